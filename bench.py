@@ -6,6 +6,12 @@ materialise the contig text (test_<rank>.dat bytes) in HBM. Inputs are generated
 copied to HBM before timing; the D2H of the contigs is outside the timed region.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2] [--n N]
+                  [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps and prints the result line. --full adds what
+  takes work of its own after the timed steps: the ground-truth check (verified_vs_truth), the
+  reference-boundary end_to_end figure, the CPU baselines and, on the forced one-rank sharded
+  line, the routed step. --dump-outputs DIR writes what the last timed step computed as .npy
+  files (dump_outputs below).
   N > 1: one rank per GPU; the table is sharded by a hash of each k-mer's minimizer, routed
          words and migrating walkers move with RCCL all-to-all (cs267_hw3_amd.dist); weak
          scaling (n k-mers per GPU). Under an outer torch.distributed.run the ranks are its
@@ -204,6 +210,37 @@ def end_to_end(table, host, n, nl, truth, steps):
                     "(H2D + insert), kh_assemble, kh_contigs_text D2H into pinned host memory"}
 
 
+DUMP_SAMPLE_BLOCKS = 64        # seeded sample of the contig text: 64 blocks of 64 KiB
+DUMP_SAMPLE_BLOCK = 1 << 16    # (4 Mi bytes -> 16 MiB as float32)
+DUMP_CHUNK = 1 << 20           # weighted byte sums cover the whole text, one per MiB
+DUMP_SEED = 20517
+
+
+def dump_outputs(path, text, counts, suffix=""):
+    """--dump-outputs: what a caller of the timed path receives after the last timed step, as
+    float arrays. `counts<suffix>.npy` (float64): n_inserted, n_contigs, n_lookups, bytes of
+    contig text. `contigs_text<suffix>.npy` (float32): the contig text (test_<rank>.dat bytes),
+    whole if it is at most 4 MiB, else DUMP_SAMPLE_BLOCKS blocks of it at offsets drawn from a
+    fixed seed and the text's length. `contigs_text_chunk_sums<suffix>.npy` (float64): for every
+    MiB of the whole text the sum of byte[i] * (i % 251 + 1), exact in float64."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    t = np.frombuffer(text, dtype=np.uint8)
+    nb = t.size
+    np.save(os.path.join(path, f"counts{suffix}.npy"),
+            np.array([counts["n_inserted"], counts["n_contigs"], counts["n_lookups"], nb], dtype=np.float64))
+    if nb <= DUMP_SAMPLE_BLOCKS * DUMP_SAMPLE_BLOCK:
+        sample = t
+    else:
+        offs = np.sort(np.random.RandomState(DUMP_SEED).randint(0, nb - DUMP_SAMPLE_BLOCK, DUMP_SAMPLE_BLOCKS))
+        sample = np.concatenate([t[o:o + DUMP_SAMPLE_BLOCK] for o in offs])
+    np.save(os.path.join(path, f"contigs_text{suffix}.npy"), sample.astype(np.float32))
+    wt = (np.arange(DUMP_CHUNK, dtype=np.int64) % 251 + 1)
+    sums = [float(np.dot(t[o:o + DUMP_CHUNK].astype(np.int64), wt[:min(DUMP_CHUNK, nb - o)]))
+            for o in range(0, nb, DUMP_CHUNK)]
+    np.save(os.path.join(path, f"contigs_text_chunk_sums{suffix}.npy"), np.array(sums, dtype=np.float64))
+
+
 def _free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -244,6 +281,11 @@ def main():
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--no-routed", action="store_true",
                     help="forced one-rank sharded line: skip the routed-step measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the ground-truth check, the "
+                         "reference-boundary end_to_end figure, the CPU baselines, the routed one-rank step")
     args = ap.parse_args()
 
     w = dict(WORKLOADS[args.workload])
@@ -263,7 +305,8 @@ def main():
     if world > 1 or os.environ.get("KH_BENCH_FORCE_DIST") == "1":
         # sharded path (also forced at one rank to exercise it on a 1-GPU box)
         from cs267_hw3_amd import dist
-        return dist.bench_main(args, w, world, rank, cpu_baseline=cpu_baseline, load_traffic=load_traffic)
+        return dist.bench_main(args, w, world, rank, cpu_baseline=cpu_baseline, load_traffic=load_traffic,
+                               dump_outputs=dump_outputs)
 
     import numpy as np
     import cs267_hw3_amd as kh
@@ -303,13 +346,20 @@ def main():
     s = phases[-1]
     nc, nl = s["n_contigs"], s["n_lookups"]
     assert s["n_inserted"] == n and nl == n - nc, s
-    truth = g.truth()
-    ok = None
-    if not args.no_verify:
-        ok = table.contigs_text() == truth
-        if not ok:
-            raise SystemExit("bench: contig text differs from the generator ground truth")
-    e2e = end_to_end(table, host, n, nl, truth, args.e2e_steps) if args.e2e_steps else None
+    text = None
+    if args.dump_outputs:
+        text = table.contigs_text()
+        dump_outputs(args.dump_outputs, text, s)
+    ok, e2e = None, None
+    if args.full:
+        truth = g.truth()
+        if not args.no_verify:
+            ok = (table.contigs_text() if text is None else text) == truth
+            if not ok:
+                raise SystemExit("bench: contig text differs from the generator ground truth")
+        if args.e2e_steps:
+            e2e = end_to_end(table, host, n, nl, truth, args.e2e_steps)
+    del text
     ops = n + nl
     value = ops / (ms / 1e3)
     avg = lambda key: sum(p[key] for p in phases) / len(phases)  # noqa: E731
@@ -359,7 +409,7 @@ def main():
         insert_pipe["traffic_GBs"] = insert_pipe["traffic"] / (ins_ms / 1e3) / 1e9
         insert_pipe["traffic_frac"] = insert_pipe["traffic_GBs"] / HBM_PEAK_GBS
     cpu = None
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         t = time.time()
         cpu = cpu_baseline(w, host, truth, min(args.cpu_sample, n))
         log(f"cpu baseline took {time.time() - t:.1f}s")

@@ -1158,10 +1158,12 @@ def run_threaded(k, recs, nranks, device=0, info=None, insert_chunks=None, shard
     return out if seq else out[0]
 
 
-def bench_main(args, w, world, rank, cpu_baseline=None, load_traffic=None):
+def bench_main(args, w, world, rank, cpu_baseline=None, load_traffic=None, dump_outputs=None):
     """bench.py body for N > 1 ranks (torch.distributed.run, one rank per GPU), or forced at one
     rank (KH_BENCH_FORCE_DIST=1). Weak scaling (n k-mers per GPU) unless the workload is strong
-    (C4: n k-mers in all, block split over the ranks, read_kmers.hpp:55-58)."""
+    (C4: n k-mers in all, block split over the ranks, read_kmers.hpp:55-58). The ground-truth
+    check, the routed one-rank step and the CPU baseline run under --full only; --dump-outputs
+    writes every rank's contig text of the last timed step (bench.dump_outputs, suffix _rank<r>)."""
     import json
     import os
     import sys
@@ -1252,8 +1254,13 @@ def bench_main(args, w, world, rank, cpu_baseline=None, load_traffic=None):
     tot = torch.tensor([st["n_starts"], st["n_lookups"]], dtype=torch.int64, device="cuda")
     dist.all_reduce(tot)
     nc, nl = tot.tolist()
+    full = getattr(args, "full", False)
+    if dump_outputs is not None and getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, dm.contigs_text(),
+                     dict(n_inserted=st["n_inserted"], n_contigs=st["n_starts"], n_lookups=st["n_lookups"]),
+                     suffix=f"_rank{rank}")
     ok = None
-    truth = None if args.no_verify else g.truth(b, e)
+    truth = g.truth(b, e) if full and not args.no_verify else None
 
     def verify():
         ok_local = int(dm.contigs_text() == truth)
@@ -1266,7 +1273,7 @@ def bench_main(args, w, world, rank, cpu_baseline=None, load_traffic=None):
     if truth is not None:
         ok = verify()
     routed = None
-    if world == 1 and not dm.ROUTE_ONE_RANK and not getattr(args, "no_routed", False):
+    if full and world == 1 and not dm.ROUTE_ONE_RANK and not getattr(args, "no_routed", False):
         # The step P > 1 runs, at one rank: records through the one-pass route and the receiver's
         # k_win1 + k_win2 (KH_DIST_ROUTE_ONE_RANK=1) instead of the single-GPU records pass.
         # Timed after the headline steps, same bracket; not part of `value`.
@@ -1285,7 +1292,7 @@ def bench_main(args, w, world, rank, cpu_baseline=None, load_traffic=None):
                   "verified_vs_truth": verify() if truth is not None else None}
         dm.ROUTE_ONE_RANK = False
     cpu = None
-    if rank == 0 and cpu_baseline is not None and not args.no_cpu:
+    if full and rank == 0 and cpu_baseline is not None and not args.no_cpu:
         # the CPU restatement of the reference on a bounded sample of the same generator/config
         # (whole contigs: a rank's block of shuffled records is not a closed set), rank 0 only,
         # after the timed region; the other ranks wait at the closing barrier

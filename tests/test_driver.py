@@ -97,7 +97,7 @@ def test_bench_multiprocess(tmp_path):
     ground-truth check on every rank, roofline and phases from rank 0."""
     import json
     r = _torchrun(2, 29551, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--kmers", "2000000", "--steps", "2",
-                             "--warmup", "1", "--no-cpu", "--e2e-steps", "0"], tmp_path, _shared_gpu_env())
+                             "--warmup", "1", "--full", "--no-cpu", "--e2e-steps", "0"], tmp_path, _shared_gpu_env())
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][0])
     assert line["n_gpus"] == 2 and line["verified_vs_truth"] is True
@@ -115,7 +115,7 @@ def test_bench_self_launch(tmp_path):
     for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(v, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--kmers", "2000000",
-                        "--steps", "2", "--warmup", "1", "--no-cpu", "--e2e-steps", "0"], cwd=tmp_path,
+                        "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--e2e-steps", "0"], cwd=tmp_path,
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][0])
@@ -151,7 +151,7 @@ def test_bench_forced_one_rank_routed(tmp_path):
     its text against the ground truth."""
     import json
     r = _torchrun(1, 29553, [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--kmers", "2000000", "--steps", "2",
-                             "--warmup", "1", "--no-cpu", "--e2e-steps", "0"], tmp_path,
+                             "--warmup", "1", "--full", "--no-cpu", "--e2e-steps", "0"], tmp_path,
                   dict(os.environ, PYTHONPATH=ROOT, KH_BENCH_FORCE_DIST="1"))
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][0])

@@ -4,9 +4,10 @@
 set -eo pipefail
 export TMPDIR=/tmp
 TAG=${1:-head}
-mkdir -p gpurun_out
-( while true; do sleep 50; date >> gpurun_out/heartbeat.log; done ) &
+OUT=${OUT:-bench_out}
+mkdir -p $OUT
+( while true; do sleep 50; date >> $OUT/heartbeat.log; done ) &
 HB=$!
 trap 'kill $HB' EXIT
-timeout -k 10 500 python bench.py > gpurun_out/bench_$TAG.log 2>&1
+timeout -k 10 500 python bench.py --full > $OUT/bench_$TAG.log 2>&1
 bash tools/profile_round.sh $TAG

@@ -5,11 +5,11 @@ set -eo pipefail
 export TMPDIR=/tmp
 O=gpurun_out/sweep
 mkdir -p $O
-B="--steps 5 --warmup 2 --e2e-steps 0"
+B="--full --steps 5 --warmup 2 --e2e-steps 0"
 ( while true; do sleep 50; date >> gpurun_out/heartbeat.log; done ) &
 HB=$!
 trap 'kill $HB' EXIT
-timeout -k 10 400 python bench.py --steps 5 --warmup 2 > $O/bench_c3.json.log 2>&1
+timeout -k 10 400 python bench.py --full --steps 5 --warmup 2 > $O/bench_c3.json.log 2>&1
 timeout -k 10 300 python bench.py $B --no-cpu --load 0.85 > $O/bench_c3_l085.json.log 2>&1
 timeout -k 10 300 python bench.py $B --no-cpu --workload c2 > $O/bench_c2.json.log 2>&1
 timeout -k 10 300 python bench.py $B --no-cpu --workload c5 > $O/bench_c5.json.log 2>&1
