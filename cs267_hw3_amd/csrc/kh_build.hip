@@ -1633,11 +1633,14 @@ hipError_t launch_route_win(const KParams& p, const uint8_t* recs, uint64_t n, u
                             unsigned long long* ctr, unsigned long long* stats, hipStream_t s,
                             unsigned long long* spl) {
     if (win < n || win >= (1ull << 32) || p.R > 15) return hipErrorInvalidValue;  // 64 records in 62 blocks
-    if (p.W == 1)
-        return p.P == 5 ? route_win_launch<1, 5>(p, recs, n, P, words, win, cnt, counts, start_mask, ctr, stats, s, spl)
-                        : route_win_launch<1, 0>(p, recs, n, P, words, win, cnt, counts, start_mask, ctr, stats, s, spl);
-    return p.P == 13 ? route_win_launch<2, 13>(p, recs, n, P, words, win, cnt, counts, start_mask, ctr, stats, s, spl)
-                     : route_win_launch<2, 0>(p, recs, n, P, words, win, cnt, counts, start_mask, ctr, stats, s, spl);
+    return with_w(p.W, [&](auto w) {
+        constexpr int W = decltype(w)::value, PK = W == 2 ? 13 : 5;  // the packed size with a parse of its own
+        auto go = [&](auto pk) {
+            return route_win_launch<W, decltype(pk)::value>(p, recs, n, P, words, win, cnt, counts, start_mask, ctr, stats,
+                                                            s, spl);
+        };
+        return p.P == PK ? go(std::integral_constant<int, PK>{}) : go(std::integral_constant<int, 0>{});
+    });
 }
 
 // pass 2: bucket -> region windows (RC words each)
@@ -2296,8 +2299,9 @@ static hipError_t part_stage(const KParams& p, const uint64_t* words, uint64_t m
 hipError_t launch_part_stage(const KParams& p, const uint64_t* words, uint64_t m, uint64_t total, bool first,
                              const PartBuffers& b, unsigned long long* ctr, unsigned long long* stats,
                              hipStream_t s, uint64_t* wsplits, uint64_t wsplits_cap, bool sample, uint64_t cap) {
-    return p.W == 1 ? part_stage<1>(p, words, m, total, first, b, ctr, stats, s, wsplits, wsplits_cap, sample, cap)
-                    : part_stage<2>(p, words, m, total, first, b, ctr, stats, s, wsplits, wsplits_cap, sample, cap);
+    return with_w(p.W, [&](auto w) {
+        return part_stage<decltype(w)::value>(p, words, m, total, first, b, ctr, stats, s, wsplits, wsplits_cap, sample, cap);
+    });
 }
 
 // Staged build from reference records (kh_insert's chunked host upload): the chunk is converted
@@ -2363,17 +2367,18 @@ hipError_t launch_part_stage_recs(const KParams& p, const uint8_t* recs, uint64_
                                   const PartBuffers& b, uint64_t* words_tmp, uint64_t* start_mask,
                                   uint64_t* split_mask, unsigned long long* ctr, unsigned long long* stats,
                                   hipStream_t s, bool sample, uint64_t cap) {
-    return p.W == 1 ? part_stage_recs<1>(p, recs, m, total, first, b, words_tmp, start_mask, split_mask, ctr, stats, s,
-                                         sample, cap)
-                    : part_stage_recs<2>(p, recs, m, total, first, b, words_tmp, start_mask, split_mask, ctr, stats, s,
-                                         sample, cap);
+    return with_w(p.W, [&](auto w) {
+        return part_stage_recs<decltype(w)::value>(p, recs, m, total, first, b, words_tmp, start_mask, split_mask, ctr,
+                                                   stats, s, sample, cap);
+    });
 }
 
 hipError_t launch_part_finish(const KParams& p, uint64_t total, TableView t, bool table_empty,
                               const PartBuffers& b, unsigned long long* ctr, unsigned long long* stats,
                               hipStream_t s) {
-    return p.W == 1 ? build_launch<1>(p, total, t, table_empty, b, ctr, stats, s)
-                    : build_launch<2>(p, total, t, table_empty, b, ctr, stats, s);
+    return with_w(p.W, [&](auto w) {
+        return build_launch<decltype(w)::value>(p, total, t, table_empty, b, ctr, stats, s);
+    });
 }
 
 hipError_t launch_part_insert(const KParams& p, const uint8_t* recs, const uint64_t* words, uint64_t n,
@@ -2383,16 +2388,14 @@ hipError_t launch_part_insert(const KParams& p, const uint8_t* recs, const uint6
                               uint64_t* wsplits, uint64_t wsplits_cap, hipEvent_t before_build,
                               hipEvent_t after_hot) {
     if (n == 0) return hipSuccess;
-    if (recs) {
-        return p.W == 1 ? part_insert<1, true>(p, recs, nullptr, n, t, table_empty, b, start_mask, split_mask, ctr,
-                                               stats, s, after_records, nullptr, 0, before_build, after_hot)
-                        : part_insert<2, true>(p, recs, nullptr, n, t, table_empty, b, start_mask, split_mask, ctr,
-                                               stats, s, after_records, nullptr, 0, before_build, after_hot);
-    }
-    return p.W == 1 ? part_insert<1, false>(p, nullptr, words, n, t, table_empty, b, nullptr, nullptr, ctr, stats, s,
-                                            nullptr, wsplits, wsplits_cap, before_build)
-                    : part_insert<2, false>(p, nullptr, words, n, t, table_empty, b, nullptr, nullptr, ctr, stats, s,
-                                            nullptr, wsplits, wsplits_cap, before_build);
+    return with_w(p.W, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        if (recs)
+            return part_insert<W, true>(p, recs, nullptr, n, t, table_empty, b, start_mask, split_mask, ctr, stats, s,
+                                        after_records, nullptr, 0, before_build, after_hot);
+        return part_insert<W, false>(p, nullptr, words, n, t, table_empty, b, nullptr, nullptr, ctr, stats, s, nullptr,
+                                     wsplits, wsplits_cap, before_build);
+    });
 }
 
 }  // namespace kh

@@ -184,6 +184,30 @@ KH_HD uint32_t key_base(Key k, int i, const KParams& p) {
     return (uint32_t)(k.lo >> sh) & 3u;
 }
 
+// bits [sh, sh + 64) of V = hi * 2^62 + lo
+KH_HD uint64_t key_bits64(Key k, uint32_t sh) {
+    return sh < 62 ? (k.lo >> sh) | (sh ? k.hi << (62 - sh) : k.hi << 62) : k.hi >> (sh - 62);
+}
+// reverse the order of the 32 2-bit groups of x
+KH_HD uint64_t rev2_64(uint64_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint64_t r = ((uint64_t)__builtin_bitreverse32((uint32_t)x) << 32) | __builtin_bitreverse32((uint32_t)(x >> 32));
+    return ((r >> 1) & 0x5555555555555555ull) | ((r & 0x5555555555555555ull) << 1);
+#else
+    x = (x >> 32) | (x << 32);
+    x = ((x >> 16) & 0x0000FFFF0000FFFFull) | ((x & 0x0000FFFF0000FFFFull) << 16);
+    x = ((x >> 8) & 0x00FF00FF00FF00FFull) | ((x & 0x00FF00FF00FF00FFull) << 8);
+    x = ((x >> 4) & 0x0F0F0F0F0F0F0F0Full) | ((x & 0x0F0F0F0F0F0F0F0Full) << 4);
+    return ((x >> 2) & 0x3333333333333333ull) | ((x & 0x3333333333333333ull) << 2);
+#endif
+}
+// The m (1..32) oldest of the last n bases of k, base i at bits 2i: a chain record's tail key
+// carries its run's bases (kh_build.hip), the walkers append them a 32-base word at a time.
+KH_HD uint64_t key_tail_piece(Key k, uint32_t n, uint32_t m) {
+    const uint64_t x = key_bits64(k, 2 * (n - m));
+    return rev2_64(m >= 32 ? x : x & ((1ull << (2 * m)) - 1)) >> (64 - 2 * m);
+}
+
 // kmer_t.hpp:51-53 next_kmer on the integer form.
 KH_HD Key key_next(Key k, uint32_t code, const KParams& p) {
     Key n;

@@ -1,5 +1,6 @@
 // kh_device.hpp — device helpers shared by the kernel translation units (not part of the ABI):
-// block scan + 3-kernel exclusive scan, slot load, CAS insert, and the read-only probe.
+// W/K launch dispatch, block scan + 3-kernel exclusive scan, slot load, the walkers' quad probe,
+// CAS insert, and the read-only probe.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -30,6 +31,19 @@ inline auto with_kt(int K, F&& f) {
         if (K == 19) return f(std::integral_constant<int, 19>{});
     }
     return f(std::integral_constant<int, 0>{});
+}
+// ... to the slot width: f(integral_constant<W>) ...
+template <class F>
+inline auto with_w(int W, F&& f) {
+    if (W == 1) return f(std::integral_constant<int, 1>{});
+    return f(std::integral_constant<int, 2>{});
+}
+// ... and to both: f(integral_constant<W>, integral_constant<KT>)
+template <class F>
+inline auto with_wkt(const KParams& p, F&& f) {
+    return with_w(p.W, [&](auto w) {
+        return with_kt<decltype(w)::value>(p.K, [&](auto kt) { return f(w, kt); });
+    });
 }
 
 __device__ __forceinline__ uint32_t lane_id() { return __lane_id(); }
@@ -69,24 +83,6 @@ __device__ __forceinline__ uint32_t wave_count_add(uint32_t* cnt, uint32_t key, 
     if (in_grp) return old + mbcnt64(grp);
     return want ? atomicAdd(&cnt[key], 1u) : 0u;
 }
-
-// Quad (4-lane) exchanges by DPP: the walkers' transposed block probes (k_walk_q, k_mw_run).
-template <int CTRL>
-__device__ __forceinline__ uint32_t qperm32(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
-}
-template <int J>
-__device__ __forceinline__ uint64_t qbcast64(uint64_t v) {  // value of quad lane J
-    constexpr int C = J * 0x55;  // quad_perm [J,J,J,J]
-    return ((uint64_t)qperm32<C>((uint32_t)(v >> 32)) << 32) | qperm32<C>((uint32_t)v);
-}
-__device__ __forceinline__ uint32_t qor32(uint32_t v) {
-    v |= qperm32<0xB1>(v);  // [1,0,3,2]
-    v |= qperm32<0x4E>(v);  // [2,3,0,1]
-    return v;
-}
-static constexpr uint64_t WQ_REC = 1ull << 63;  // walker's next load is a head record (index below)
-static constexpr uint64_t WQ_IDLE = ~0ull;
 
 // Rank of each wanting lane among all lanes (of any wave) that add to cnt[key]: one atomic per
 // distinct key in the wave (a loop over the wave's keys), so few keys (the route's owner ranks,
@@ -327,6 +323,99 @@ __device__ __forceinline__ void load_slot_nt(const uint64_t* slots, uint64_t s, 
         w0 = __builtin_nontemporal_load(slots + s);
         w1 = 0;
     }
+}
+
+// Quad (4-lane) exchanges by DPP (ALU, no LDS).
+template <int CTRL>
+__device__ __forceinline__ uint32_t qperm32(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
+}
+template <int J>
+__device__ __forceinline__ uint64_t qbcast64(uint64_t v) {  // value of quad lane J
+    constexpr int C = J * 0x55;  // quad_perm [J,J,J,J]
+    return ((uint64_t)qperm32<C>((uint32_t)(v >> 32)) << 32) | qperm32<C>((uint32_t)v);
+}
+__device__ __forceinline__ uint32_t qor32(uint32_t v) {
+    v |= qperm32<0xB1>(v);  // [1,0,3,2]
+    v |= qperm32<0x4E>(v);  // [2,3,0,1]
+    return v;
+}
+static constexpr uint64_t WQ_REC = 1ull << 63;  // walker's next load is a head record (index below)
+static constexpr uint64_t WQ_IDLE = ~0ull;
+
+// Quad-transposed block probe, the one load step of the walkers (k_walk_q, k_mw_run; k_rec_succ
+// keeps a reduced copy, see there). Every lane of the wave calls it once per loop iteration with its
+// probe word sp: a slot position (look k up from there), WQ_REC | index (read that head record)
+// or WQ_IDLE. Each lane's sp and key are broadcast to its quad; lane q of the quad
+// loads slot q of every member's 4-slot block (64 B at 16-B slots: one request per block instead of
+// one per slot, ~1.06 random requests per lookup against ~1.3 slot by slot), the members learn
+// their first hit / first EMPTY at or after sp by ballot, and the hit slot's extension and
+// head-record index (chains only) come back by a quad OR-reduction. A record read loads the same
+// 16 B in all 4 lanes (one request). The caller acts on the result: hit when fh < fe, absent when
+// fe < 4, else the next block.
+struct QuadProbe {
+    uint32_t fh, fe;  // first hit / first EMPTY among the lane's block slots (4 = none)
+    uint32_t ext;     // hit slot: ext | found flag 0x40 | head-record index << 7
+    uint64_t r0, r1;  // the words this lane loaded for itself (a record read: the record)
+};
+// q, ql: the lane's quad member (lane & 3) and its quad's first lane (lane & ~3), computed by the
+// kernel before its loop (computed in here, k_mw_run took 1-2 more VGPRs)
+template <int W>
+__device__ __forceinline__ QuadProbe quad_probe(uint64_t sp, Key k, const uint64_t* __restrict__ slots,
+                                                uint64_t cap, const uint64_t* headrec, const KParams& p,
+                                                bool chains, uint32_t q, uint32_t ql) {
+    uint64_t sj[4], w0[4], w1[4];
+    sj[0] = qbcast64<0>(sp);
+    sj[1] = qbcast64<1>(sp);
+    sj[2] = qbcast64<2>(sp);
+    sj[3] = qbcast64<3>(sp);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        w0[j] = EMPTY;
+        w1[j] = 0;
+        if (sj[j] == WQ_IDLE) continue;
+        if (sj[j] & WQ_REC) {
+            const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(headrec + (sj[j] & ~WQ_REC) * 2);
+            w0[j] = v.x;
+            w1[j] = v.y;
+        } else {
+            const uint64_t my = (sj[j] & ~3ull) + q;
+            if (my < cap) load_slot_nt<W>(slots, my, w0[j], w1[j]);
+        }
+    }
+    uint64_t kh_[4], kl_[4];
+    kh_[0] = qbcast64<0>(k.hi);
+    kh_[1] = qbcast64<1>(k.hi);
+    kh_[2] = qbcast64<2>(k.hi);
+    kh_[3] = qbcast64<3>(k.hi);
+    kl_[0] = qbcast64<0>(k.lo);
+    kl_[1] = qbcast64<1>(k.lo);
+    kl_[2] = qbcast64<2>(k.lo);
+    kl_[3] = qbcast64<3>(k.lo);
+    QuadProbe r{4u, 4u, 0u, 0ull, 0ull};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint64_t my = (sj[j] & ~3ull) + q;
+        const bool probe_j = sj[j] != WQ_IDLE && !(sj[j] & WQ_REC);
+        const bool valid = probe_j && my >= sj[j] && my < cap;
+        const bool empty = w0[j] == EMPTY;
+        const bool hit = !empty & (slot_keybits(w0[j], p) == ((W == 1) ? kl_[j] : kh_[j])) &
+                         ((W == 1) | (w1[j] == kl_[j]));
+        const uint32_t bh = (uint32_t)(__ballot(valid && hit) >> ql) & 0xFu;
+        const uint32_t be = (uint32_t)(__ballot(valid && empty) >> ql) & 0xFu;
+        const uint32_t fh = bh ? (uint32_t)__builtin_ctz(bh) : 4u;
+        const uint32_t fe = be ? (uint32_t)__builtin_ctz(be) : 4u;
+        const uint32_t ext =
+            qor32(q == fh ? (slot_ext(w0[j]) | 0x40u | ((chains ? slot_hidx(w0[j], p) : 0u) << 7)) : 0u);
+        if (q == (uint32_t)j) {
+            r.fh = fh;
+            r.fe = fe;
+            r.ext = ext;
+            r.r0 = w0[j];
+            r.r1 = w1[j];
+        }
+    }
+    return r;
 }
 
 // w0: the slot's word0 (may carry j*); home: its home slot (home_of)

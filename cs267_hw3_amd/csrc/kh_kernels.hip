@@ -62,10 +62,9 @@ hipError_t launch_insert(const KParams& p, const uint8_t* recs, uint64_t n, Tabl
     if (n == 0) return hipSuccess;
     const uint64_t ntiles = (n + BLOCK - 1) / BLOCK;
     const unsigned grid = (unsigned)hmin(ntiles, 256ull * 32);
-    if (p.W == 1)
-        k_insert<1><<<grid, BLOCK, 0, s>>>(p, recs, n, t.slots, t.cap, start_mask, split_mask, stats);
-    else
-        k_insert<2><<<grid, BLOCK, 0, s>>>(p, recs, n, t.slots, t.cap, start_mask, split_mask, stats);
+    with_w(p.W, [&](auto w) {
+        k_insert<decltype(w)::value><<<grid, BLOCK, 0, s>>>(p, recs, n, t.slots, t.cap, start_mask, split_mask, stats);
+    });
     return hipGetLastError();
 }
 
@@ -130,10 +129,9 @@ hipError_t launch_collect_starts(const KParams& p, const uint8_t* recs, uint64_t
                                   (unsigned long long*)nullptr, s);
     if (e != hipSuccess) return e;
     const unsigned grid = (unsigned)hmin((nw + BLOCK - 1) / BLOCK, 4096);
-    if (p.W == 1)
-        k_scatter_starts<1><<<grid, BLOCK, 0, s>>>(p, recs, n, start_mask, mask_offsets, starts);
-    else
-        k_scatter_starts<2><<<grid, BLOCK, 0, s>>>(p, recs, n, start_mask, mask_offsets, starts);
+    with_w(p.W, [&](auto w) {
+        k_scatter_starts<decltype(w)::value><<<grid, BLOCK, 0, s>>>(p, recs, n, start_mask, mask_offsets, starts);
+    });
     return hipGetLastError();
 }
 
@@ -156,10 +154,7 @@ hipError_t launch_load_starts(const KParams& p, const uint8_t* recs, uint64_t n,
                               unsigned long long* ctr, hipStream_t s) {
     if (n) {
         const unsigned grid = (unsigned)hmin((n + BLOCK - 1) / BLOCK, 4096);
-        if (p.W == 1)
-            k_load_starts<1><<<grid, BLOCK, 0, s>>>(p, recs, n, starts);
-        else
-            k_load_starts<2><<<grid, BLOCK, 0, s>>>(p, recs, n, starts);
+        with_w(p.W, [&](auto w) { k_load_starts<decltype(w)::value><<<grid, BLOCK, 0, s>>>(p, recs, n, starts); });
     }
     k_set_ctr<<<1, 1, 0, s>>>(ctr, CT_N_STARTS, (unsigned long long)n);
     return hipGetLastError();
@@ -189,10 +184,7 @@ hipError_t launch_find(const KParams& p, const uint8_t* keys, uint64_t n, TableV
                        uint8_t* found, hipStream_t s) {
     if (n == 0) return hipSuccess;
     const unsigned grid = (unsigned)hmin((n + BLOCK - 1) / BLOCK, 8192);
-    if (p.W == 1)
-        k_find<1><<<grid, BLOCK, 0, s>>>(p, keys, n, t.slots, t.cap, out, found);
-    else
-        k_find<2><<<grid, BLOCK, 0, s>>>(p, keys, n, t.slots, t.cap, out, found);
+    with_w(p.W, [&](auto w) { k_find<decltype(w)::value><<<grid, BLOCK, 0, s>>>(p, keys, n, t.slots, t.cap, out, found); });
     return hipGetLastError();
 }
 
@@ -226,10 +218,10 @@ __device__ __forceinline__ uint64_t chunk_word(uint64_t ch, uint32_t w, uint64_t
     return (uint64_t)w * chunk_cap + ch;
 }
 
-// Append base `b` as base number `steps` of contig c (2 bits, 32 per word, 8 words per chunk).
-__device__ __forceinline__ void append_base(const LaneOut& o, uint64_t c, uint32_t b, uint32_t& steps,
-                                            uint32_t& chunk, uint64_t& buf, unsigned long long* ctr,
-                                            unsigned long long* stats) {
+// The chunk that base number `steps` of contig c goes to: its own first chunk, a new one from the
+// counter at every further chunk boundary, else the current one.
+__device__ __forceinline__ void next_chunk(const LaneOut& o, uint64_t c, uint32_t steps, uint32_t& chunk,
+                                           unsigned long long* ctr, unsigned long long* stats) {
     if (steps == 0) {
         chunk = (uint32_t)c;
     } else if ((steps & (CHUNK_BASES - 1)) == 0) {
@@ -241,6 +233,13 @@ __device__ __forceinline__ void append_base(const LaneOut& o, uint64_t c, uint32
             atomicAdd(&stats[ST_CHUNK_OVF], 1ull);
         }
     }
+}
+
+// Append base `b` as base number `steps` of contig c (2 bits, 32 per word, 8 words per chunk).
+__device__ __forceinline__ void append_base(const LaneOut& o, uint64_t c, uint32_t b, uint32_t& steps,
+                                            uint32_t& chunk, uint64_t& buf, unsigned long long* ctr,
+                                            unsigned long long* stats) {
+    next_chunk(o, c, steps, chunk, ctr, stats);
     buf |= (uint64_t)b << (2 * (steps & 31));
     if ((steps & 31) == 31) {
         if (chunk < o.chunk_cap) o.chunk_data[chunk_word(chunk, (steps >> 5) & 7, o.chunk_cap)] = buf;
@@ -253,17 +252,7 @@ __device__ __forceinline__ void append_base(const LaneOut& o, uint64_t c, uint32
 __device__ __forceinline__ void append_run(const LaneOut& o, uint64_t c, uint64_t piece, uint32_t m, uint32_t& steps,
                                            uint32_t& chunk, uint64_t& buf, unsigned long long* ctr,
                                            unsigned long long* stats) {
-    if (steps == 0) {
-        chunk = (uint32_t)c;
-    } else if ((steps & (CHUNK_BASES - 1)) == 0) {
-        chunk = (uint32_t)(o.n_first + atomicAdd(&ctr[CT_CHUNK_NEXT], 1ull));
-        if (chunk < o.chunk_cap) {
-            o.chunk_owner[chunk] = (uint32_t)c;
-            o.chunk_seq[chunk] = steps / CHUNK_BASES;
-        } else {
-            atomicAdd(&stats[ST_CHUNK_OVF], 1ull);
-        }
-    }
+    next_chunk(o, c, steps, chunk, ctr, stats);
     buf |= piece << (2 * (steps & 31));
     steps += m;
     if ((steps & 31) == 0) {
@@ -272,15 +261,6 @@ __device__ __forceinline__ void append_run(const LaneOut& o, uint64_t c, uint64_
     }
 }
 
-// bits [sh, sh + 64) of V = hi * 2^62 + lo
-__device__ __forceinline__ uint64_t key_bits64(Key k, uint32_t sh) {
-    return sh < 62 ? (k.lo >> sh) | (sh ? k.hi << (62 - sh) : k.hi << 62) : k.hi >> (sh - 62);
-}
-// reverse the order of the 32 2-bit groups of x
-__device__ __forceinline__ uint64_t rev2_64(uint64_t x) {
-    const uint64_t r = ((uint64_t)__builtin_bitreverse32((uint32_t)x) << 32) | __builtin_bitreverse32((uint32_t)(x >> 32));
-    return ((r >> 1) & 0x5555555555555555ull) | ((r & 0x5555555555555555ull) << 1);
-}
 // Append the last n bases of k (oldest first): the links of a chain record (kh_build.hip).
 __device__ __forceinline__ void append_key_tail(const LaneOut& o, uint64_t c, Key k, uint32_t n, uint32_t& steps,
                                                 uint32_t& chunk, uint64_t& buf, unsigned long long* ctr,
@@ -288,9 +268,7 @@ __device__ __forceinline__ void append_key_tail(const LaneOut& o, uint64_t c, Ke
     while (n) {
         const uint32_t room = 32u - (steps & 31u);
         const uint32_t m = n < room ? n : room;
-        const uint64_t x = key_bits64(k, 2 * (n - m));
-        const uint64_t piece = rev2_64(m >= 32 ? x : x & ((1ull << (2 * m)) - 1)) >> (64 - 2 * m);
-        append_run(o, c, piece, m, steps, chunk, buf, ctr, stats);
+        append_run(o, c, key_tail_piece(k, n, m), m, steps, chunk, buf, ctr, stats);
         n -= m;
     }
 }
@@ -308,13 +286,9 @@ __device__ __forceinline__ uint64_t walk_splits(const WalkBuffers& wb) {
 
 // ---------------------------------------------------------------------------------------------
 // Quad-transposed walker: one walker per lane, every probe reads the walker's whole 4-slot block
-// (64 B at 16-B slots): lane q of a quad loads slot q of the block of each of the quad's 4
-// walkers, so a lookup costs ~1.06 random requests instead of ~1.3 for slot-by-slot probes
-// (linear-probing displacement crossing a slot). The walk is bound by the number of random line
+// with its quad (quad_probe, kh_device.hpp). The walk is bound by the number of random line
 // requests the memory system serves (~51 G/s whether a request is a 16-B slot or a full 128-B
-// line: tools/membench chase16 / chase64q / chase128o). All intra-quad exchange is DPP quad_perm
-// (ALU, no LDS): each walker's probe position and key are broadcast to its quad, and the hit
-// slot's extension comes back by a quad OR-reduction.
+// line: tools/membench chase16 / chase64q / chase128o).
 //
 // Chains (kh_build.hip region_chains): a looked-up k-mer whose slot carries a head-record index
 // is the head of a run of k-mers that share its minimizer; the walker then reads the record
@@ -491,69 +465,14 @@ __global__ __launch_bounds__(BLOCK) void k_walk_q(KParams p_in, const uint64_t* 
             resolved = false;
             do_place = false;
         }
-        // -- quad loads: a probe reads 4 slots per lane, one per quad member's block; a record
-        //    read loads the same 16 B in all 4 lanes (one request) ------------------------------
-        const uint64_t sp = active ? s : WQ_IDLE;
-        uint64_t sj[4], w0[4], w1[4];
-        sj[0] = qbcast64<0>(sp);
-        sj[1] = qbcast64<1>(sp);
-        sj[2] = qbcast64<2>(sp);
-        sj[3] = qbcast64<3>(sp);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            w0[j] = EMPTY;
-            w1[j] = 0;
-            if (sj[j] == WQ_IDLE) continue;
-            if (sj[j] & WQ_REC) {
-                const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(wb.headrec + (sj[j] & ~WQ_REC) * 2);
-                w0[j] = v.x;
-                w1[j] = v.y;
-            } else {
-                const uint64_t my = (sj[j] & ~3ull) + q;
-                if (my < cap) load_slot_nt<W>(slots, my, w0[j], w1[j]);
-            }
-        }
-        uint64_t kh_[4], kl_[4];
-        kh_[0] = qbcast64<0>(k.hi);
-        kh_[1] = qbcast64<1>(k.hi);
-        kh_[2] = qbcast64<2>(k.hi);
-        kh_[3] = qbcast64<3>(k.hi);
-        kl_[0] = qbcast64<0>(k.lo);
-        kl_[1] = qbcast64<1>(k.lo);
-        kl_[2] = qbcast64<2>(k.lo);
-        kl_[3] = qbcast64<3>(k.lo);
-        uint32_t myfh = 4, myfe = 4, myext = 0;
-        uint64_t r0 = 0, r1 = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint64_t my = (sj[j] & ~3ull) + q;
-            const bool probe_j = sj[j] != WQ_IDLE && !(sj[j] & WQ_REC);
-            const bool valid = probe_j && my >= sj[j] && my < cap;
-            const bool empty = w0[j] == EMPTY;
-            const bool hit = !empty & (slot_keybits(w0[j], p) == ((W == 1) ? kl_[j] : kh_[j])) &
-                             ((W == 1) | (w1[j] == kl_[j]));
-            const uint32_t bh = (uint32_t)(__ballot(valid && hit) >> ql) & 0xFu;
-            const uint32_t be = (uint32_t)(__ballot(valid && empty) >> ql) & 0xFu;
-            const uint32_t fh = bh ? (uint32_t)__builtin_ctz(bh) : 4u;
-            const uint32_t fe = be ? (uint32_t)__builtin_ctz(be) : 4u;
-            // hit slot: ext | found flag | head-record index << 7
-            const uint32_t ext =
-                qor32(q == fh ? (slot_ext(w0[j]) | 0x40u | ((chains ? slot_hidx(w0[j], p) : 0u) << 7)) : 0u);
-            if (q == (uint32_t)j) {
-                myfh = fh;
-                myfe = fe;
-                myext = ext;
-                r0 = w0[j];
-                r1 = w1[j];
-            }
-        }
+        const QuadProbe pr = quad_probe<W>(active ? s : WQ_IDLE, k, slots, cap, wb.headrec, p, chains, q, ql);
         if (active) {
             if (s & WQ_REC) {
                 // head record: jump to the run's tail, appending the bases of its links
-                k = slot_key(r0, r1, p);
-                fwd = ext_fwd(slot_ext(r0));
-                const uint32_t links = rec_links(r0, p);
-                nrec = rec_succ(r0, p);
+                k = slot_key(pr.r0, pr.r1, p);
+                fwd = ext_fwd(slot_ext(pr.r0));
+                const uint32_t links = rec_links(pr.r0, p);
+                nrec = rec_succ(pr.r0, p);
                 append_key_tail(o, c, k, links, steps, chunk, buf, ctr, stats);
                 resolved = true;
                 if (steps > wb.max_steps) {
@@ -561,8 +480,8 @@ __global__ __launch_bounds__(BLOCK) void k_walk_q(KParams p_in, const uint64_t* 
                     finish_contig(o, c, steps, chunk, buf);
                     active = false;
                 }
-            } else if (myfh < myfe) {
-                const uint32_t hidx = myext >> 7, tf = ext_fwd(myext & 63u);
+            } else if (pr.fh < pr.fe) {
+                const uint32_t hidx = pr.ext >> 7, tf = ext_fwd(pr.ext & 63u);
                 // a start walks from its own record (kmer_hash.cpp:42-44): a record whose run
                 // begins with another extension (duplicate key) is not used for it
                 if (hidx && !(entry && tf != fwd)) {
@@ -577,7 +496,7 @@ __global__ __launch_bounds__(BLOCK) void k_walk_q(KParams p_in, const uint64_t* 
                     }
                 }
                 entry = false;
-            } else if (myfe < 4u || ++pb > pb_max) {
+            } else if (pr.fe < 4u || ++pb > pb_max) {
                 if (entry) {  // a start k-mer need not be in the table (kh_set_starts)
                     resolved = true;
                     entry = false;
@@ -601,9 +520,11 @@ __global__ __launch_bounds__(BLOCK) void k_walk_q(KParams p_in, const uint64_t* 
 // need no test here: the walker checks the next k-mer for one before it follows a successor.
 // Each wave owns a contiguous range of regions and keeps its 64 lanes busy with a queue over the
 // range's records (the per-region counts follow the records, written by the build): a lane reads
-// its record, then probes y's 4-slot blocks quad-transposed as the walker does (lane q of a quad
-// loads slot q of each member's 64-B block; one request per block instead of one per slot: ~1.3
-// requests per lookup slot by slot). Records of consecutive lanes are consecutive 16-B lines.
+// its record, then probes y's 4-slot blocks with its quad as the walkers do. The probe is a copy
+// of quad_probe (kh_device.hpp) that reads no records and reduces the hit slot's head index alone:
+// through quad_probe itself (its ext packing, ~57 instructions more at k=51) the C3 walk beside
+// which this kernel runs measured 2 % slower (profiles/r07/ab_walker_core.txt).
+// Records of consecutive lanes are consecutive 16-B lines.
 template <int W, int KT>
 __global__ __launch_bounds__(BLOCK) void k_rec_succ(KParams p_in, const uint64_t* __restrict__ slots, uint64_t cap,
                                                     uint64_t* headrec, uint32_t hcap) {
@@ -736,10 +657,9 @@ hipError_t launch_rec_succ(const KParams& p, TableView t, uint64_t* headrec, uin
     if (!rec_succ_fits(p, hcap)) return hipSuccess;
     // a wave per ~16 regions keeps its lanes' record queue full (the waves' ranges are contiguous)
     const unsigned grid = blocks ? blocks : (unsigned)hmin((nreg(p) + BLOCK / 64 - 1) / (BLOCK / 64), 8u * cu_count());
-    if (p.W == 1)
-        with_kt<1>(p.K, [&](auto kt) { k_rec_succ<1, decltype(kt)::value><<<grid, BLOCK, 0, s>>>(p, t.slots, t.cap, headrec, hcap); });
-    else
-        with_kt<2>(p.K, [&](auto kt) { k_rec_succ<2, decltype(kt)::value><<<grid, BLOCK, 0, s>>>(p, t.slots, t.cap, headrec, hcap); });
+    with_wkt(p, [&](auto w, auto kt) {
+        k_rec_succ<decltype(w)::value, decltype(kt)::value><<<grid, BLOCK, 0, s>>>(p, t.slots, t.cap, headrec, hcap);
+    });
     return hipGetLastError();
 }
 
@@ -764,10 +684,9 @@ hipError_t launch_walk(const KParams& p, TableView t, const WalkBuffers& wb, uns
         const uint64_t per = nq / ((uint64_t)WALK_GRAB * grid * (BLOCK / 64) * 4);
         w.batches = (uint32_t)(per < 1 ? 1 : hmin(per, (uint64_t)WALK_BATCHES));
     }
-    if (p.W == 1)
-        with_kt<1>(p.K, [&](auto kt) { k_walk_q<1, decltype(kt)::value><<<grid, BLOCK, 0, s>>>(p, t.slots, t.cap, w, ctr, stats); });
-    else
-        with_kt<2>(p.K, [&](auto kt) { k_walk_q<2, decltype(kt)::value><<<grid, BLOCK, 0, s>>>(p, t.slots, t.cap, w, ctr, stats); });
+    with_wkt(p, [&](auto wc, auto kt) {
+        k_walk_q<decltype(wc)::value, decltype(kt)::value><<<grid, BLOCK, 0, s>>>(p, t.slots, t.cap, w, ctr, stats);
+    });
     return hipGetLastError();
 }
 
@@ -1214,10 +1133,7 @@ hipError_t launch_write_heads(const KParams& p, const uint64_t* starts, uint64_t
                               const uint64_t* offsets, char* out, hipStream_t s, uint64_t cap) {
     if (nc == 0) return hipSuccess;
     const unsigned gh = (unsigned)hmin((nc * 16 + BLOCK - 1) / BLOCK, 65536);  // 16 lanes per contig
-    if (p.W == 1)
-        k_write_heads<1><<<gh, BLOCK, 0, s>>>(p, starts, nc, len, offsets, out, cap);
-    else
-        k_write_heads<2><<<gh, BLOCK, 0, s>>>(p, starts, nc, len, offsets, out, cap);
+    with_w(p.W, [&](auto w) { k_write_heads<decltype(w)::value><<<gh, BLOCK, 0, s>>>(p, starts, nc, len, offsets, out, cap); });
     return hipGetLastError();
 }
 
@@ -1233,34 +1149,20 @@ static bool launch_lines(const KParams& p, const WalkBuffers& wb, const uint32_t
     if (p.K >= LINE2_KMIN) {
         const uint64_t waves2 = (min(out_bytes, cap) + LINE2_BYTES - 1) / LINE2_BYTES;
         const unsigned g2 = (unsigned)hmin((waves2 + BLOCK / 64 - 1) / (BLOCK / 64) + 1, 8192);
-        if (p.W == 1)
-            with_kt<1>(p.K, [&](auto kt) {
-                k_write_lines32<1, decltype(kt)::value><<<g2, BLOCK, 0, s>>>(
-                    p, wb.starts, nc, clen, wb.contig_len, wb.chunk_data, wb.chunk_cap, offsets, line_first, ctr, out,
-                    cap, slen_add);
-            });
-        else
-            with_kt<2>(p.K, [&](auto kt) {
-                k_write_lines32<2, decltype(kt)::value><<<g2, BLOCK, 0, s>>>(
-                    p, wb.starts, nc, clen, wb.contig_len, wb.chunk_data, wb.chunk_cap, offsets, line_first, ctr, out,
-                    cap, slen_add);
-            });
+        with_wkt(p, [&](auto w, auto kt) {
+            k_write_lines32<decltype(w)::value, decltype(kt)::value><<<g2, BLOCK, 0, s>>>(
+                p, wb.starts, nc, clen, wb.contig_len, wb.chunk_data, wb.chunk_cap, offsets, line_first, ctr, out, cap,
+                slen_add);
+        });
         return true;
     }
     const uint64_t waves = (min(out_bytes, cap) + LINE_BYTES - 1) / LINE_BYTES;
     const unsigned gl = (unsigned)hmin((waves + BLOCK / 64 - 1) / (BLOCK / 64) + 1, 8192);
-    if (p.W == 1)
-        with_kt<1>(p.K, [&](auto kt) {
-            k_write_lines<1, decltype(kt)::value><<<gl, BLOCK, 0, s>>>(p, wb.starts, nc, clen, wb.contig_len, wb.chunk_data,
-                                                                      wb.chunk_cap, offsets, line_first, ctr, out, cap,
-                                                                      slen_add);
-        });
-    else
-        with_kt<2>(p.K, [&](auto kt) {
-            k_write_lines<2, decltype(kt)::value><<<gl, BLOCK, 0, s>>>(p, wb.starts, nc, clen, wb.contig_len, wb.chunk_data,
-                                                                      wb.chunk_cap, offsets, line_first, ctr, out, cap,
-                                                                      slen_add);
-        });
+    with_wkt(p, [&](auto w, auto kt) {
+        k_write_lines<decltype(w)::value, decltype(kt)::value><<<gl, BLOCK, 0, s>>>(
+            p, wb.starts, nc, clen, wb.contig_len, wb.chunk_data, wb.chunk_cap, offsets, line_first, ctr, out, cap,
+            slen_add);
+    });
     return true;
 }
 
@@ -1285,10 +1187,9 @@ hipError_t launch_materialize(const KParams& p, const WalkBuffers& wb, uint64_t*
     const bool lines = launch_lines(p, wb, wb.contig_len, offsets, out, ctr, s, cap, line_first, out_bytes);
     if (!lines) {
         const unsigned gh = (unsigned)hmin((nc * 16 + BLOCK - 1) / BLOCK, 65536);  // 16 lanes per contig
-        if (p.W == 1)
-            k_write_heads<1><<<gh, BLOCK, 0, s>>>(p, wb.starts, nc, wb.contig_len, offsets, out, cap);
-        else
-            k_write_heads<2><<<gh, BLOCK, 0, s>>>(p, wb.starts, nc, wb.contig_len, offsets, out, cap);
+        with_w(p.W, [&](auto w) {
+            k_write_heads<decltype(w)::value><<<gh, BLOCK, 0, s>>>(p, wb.starts, nc, wb.contig_len, offsets, out, cap);
+        });
     }
     // chunks the line writer does not cover: every contig's chunks past its first
     const uint64_t cb = lines ? nc : 0;
@@ -1772,18 +1673,17 @@ hipError_t launch_route(const KParams& p, const uint8_t* recs, uint64_t n, uint3
     unsigned long long* total = reinterpret_cast<unsigned long long*>(scratch);
     const uint64_t nb = route_blocks(n);
     if (nb == 0) return hipMemsetAsync(counts, 0, (nranks + 1) * 8, s);
-    if (p.W == 1)
-        with_kt<1>(p.K, [&](auto kt) { k_route_own<decltype(kt)::value><<<(unsigned)nb, BLOCK, 0, s>>>(p, recs, n, nranks, own, hist, start_mask, spl); });
-    else
-        with_kt<2>(p.K, [&](auto kt) { k_route_own<decltype(kt)::value><<<(unsigned)nb, BLOCK, 0, s>>>(p, recs, n, nranks, own, hist, start_mask, spl); });
+    with_wkt(p, [&](auto, auto kt) {
+        k_route_own<decltype(kt)::value><<<(unsigned)nb, BLOCK, 0, s>>>(p, recs, n, nranks, own, hist, start_mask, spl);
+    });
     hipError_t e = scan_exclusive(HistF{hist, nb, nranks}, nb * nranks, off, scratch + 1,
                                   (unsigned long long*)nullptr, total, s);
     if (e != hipSuccess) return e;
     k_route_counts<0><<<1, MAX_RANKS, 0, s>>>(off, nb, nranks, total, counts);
-    if (p.W == 1)
-        with_kt<1>(p.K, [&](auto kt) { k_route_scatter<1, decltype(kt)::value><<<(unsigned)nb, BLOCK, 0, s>>>(p, recs, n, nranks, own, off, nb, out_words); });
-    else
-        with_kt<2>(p.K, [&](auto kt) { k_route_scatter<2, decltype(kt)::value><<<(unsigned)nb, BLOCK, 0, s>>>(p, recs, n, nranks, own, off, nb, out_words); });
+    with_wkt(p, [&](auto w, auto kt) {
+        k_route_scatter<decltype(w)::value, decltype(kt)::value><<<(unsigned)nb, BLOCK, 0, s>>>(p, recs, n, nranks, own, off,
+                                                                                            nb, out_words);
+    });
     return hipGetLastError();
 }
 
@@ -1806,10 +1706,7 @@ hipError_t launch_insert_words(const KParams& p, const uint64_t* words, uint64_t
                                unsigned long long* stats, hipStream_t s) {
     if (m == 0) return hipSuccess;
     const unsigned grid = (unsigned)hmin((m + BLOCK - 1) / BLOCK, 256ull * 32);
-    if (p.W == 1)
-        k_insert_words<1><<<grid, BLOCK, 0, s>>>(p, words, m, t.slots, t.cap, stats);
-    else
-        k_insert_words<2><<<grid, BLOCK, 0, s>>>(p, words, m, t.slots, t.cap, stats);
+    with_w(p.W, [&](auto w) { k_insert_words<decltype(w)::value><<<grid, BLOCK, 0, s>>>(p, words, m, t.slots, t.cap, stats); });
     return hipGetLastError();
 }
 

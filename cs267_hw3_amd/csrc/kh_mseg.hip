@@ -85,10 +85,7 @@ hipError_t launch_split_collect(const KParams& p, const uint64_t* words, uint64_
                                 unsigned long long* ctr, hipStream_t s) {
     if (m == 0 || !p.split_bits) return hipSuccess;
     const unsigned g = (unsigned)hmin((m + SPLIT_CHUNK - 1) / SPLIT_CHUNK, 8192);
-    if (p.W == 1)
-        k_split_collect<1><<<g, BLOCK, 0, s>>>(p, words, m, out, cap, ctr);
-    else
-        k_split_collect<2><<<g, BLOCK, 0, s>>>(p, words, m, out, cap, ctr);
+    with_w(p.W, [&](auto w) { k_split_collect<decltype(w)::value><<<g, BLOCK, 0, s>>>(p, words, m, out, cap, ctr); });
     return hipGetLastError();
 }
 
@@ -120,10 +117,7 @@ hipError_t launch_mseg_stab(const KParams& p, const uint64_t* splits, uint64_t n
     hipError_t e = hipMemsetAsync(stab, 0xff, cap2 * 16, s);
     if (e != hipSuccess || nsp == 0) return e;
     const unsigned g = (unsigned)hmin((nsp + BLOCK - 1) / BLOCK, 4096);
-    if (p.W == 1)
-        k_mseg_stab<1><<<g, BLOCK, 0, s>>>(p, splits, nsp, stab, id, cap2);
-    else
-        k_mseg_stab<2><<<g, BLOCK, 0, s>>>(p, splits, nsp, stab, id, cap2);
+    with_w(p.W, [&](auto w) { k_mseg_stab<decltype(w)::value><<<g, BLOCK, 0, s>>>(p, splits, nsp, stab, id, cap2); });
     return hipGetLastError();
 }
 

@@ -43,7 +43,7 @@ __global__ __launch_bounds__(BLOCK) void k_mw_run(KParams p_in, const uint64_t* 
     if (mw.hot_on && *mw.hot_on == 0) p.hot = nullptr;  // no remapped region: skip the bitmap loads
     const bool chains = p.chain && mw.hcap != 0;
     const uint64_t n_live = mw.n_dev ? min((uint64_t)*mw.n_dev, mw.n_in) : mw.n_in;
-    const uint32_t q4 = lane_id() & 3u, ql4 = lane_id() & ~3u;  // quad member, quad's first lane
+    const uint32_t q = lane_id() & 3u, ql = lane_id() & ~3u;  // quad member, quad's first lane
     uint32_t reg = 0;  // region of the k-mer being probed (its head records live there)
     // append n bases (base i at bits 2i of piece, n <= room in the current word) to the walker's
     // buffer, flushing a finished 32-base word as a text record
@@ -199,84 +199,23 @@ __global__ __launch_bounds__(BLOCK) void k_mw_run(KParams p_in, const uint64_t* 
                 j += stride;
             }
         }
-        // quad-transposed block probe (as k_walk_q): lane q of a quad loads slot q of each member's
-        // 64-B block (one request per block), the members learn their first hit / EMPTY by ballot;
-        // a record read loads the same 16 B in all 4 lanes (one request)
-        const uint64_t sp = (active && probing) ? s : WQ_IDLE;
-        uint64_t sj[4], w0[4], w1[4];
-        sj[0] = qbcast64<0>(sp);
-        sj[1] = qbcast64<1>(sp);
-        sj[2] = qbcast64<2>(sp);
-        sj[3] = qbcast64<3>(sp);
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            w0[jj] = EMPTY;
-            w1[jj] = 0;
-            if (sj[jj] == WQ_IDLE) continue;
-            if (sj[jj] & WQ_REC) {
-                const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(mw.headrec + (sj[jj] & ~WQ_REC) * 2);
-                w0[jj] = v.x;
-                w1[jj] = v.y;
-            } else {
-                const uint64_t my = (sj[jj] & ~3ull) + q4;
-                if (my < cap) load_slot_nt<W>(slots, my, w0[jj], w1[jj]);
-            }
-        }
-        uint64_t kh_[4], kl_[4];
-        kh_[0] = qbcast64<0>(k.hi);
-        kh_[1] = qbcast64<1>(k.hi);
-        kh_[2] = qbcast64<2>(k.hi);
-        kh_[3] = qbcast64<3>(k.hi);
-        kl_[0] = qbcast64<0>(k.lo);
-        kl_[1] = qbcast64<1>(k.lo);
-        kl_[2] = qbcast64<2>(k.lo);
-        kl_[3] = qbcast64<3>(k.lo);
-        uint32_t myfh = 4, myfe = 4, myext = 0;
-        uint64_t r0 = 0, r1 = 0;
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const uint64_t my = (sj[jj] & ~3ull) + q4;
-            const bool probe_j = sj[jj] != WQ_IDLE && !(sj[jj] & WQ_REC);
-            const bool valid = probe_j && my >= sj[jj] && my < cap;
-            const bool empty = w0[jj] == EMPTY;
-            const bool hit = !empty & (slot_keybits(w0[jj], p) == ((W == 1) ? kl_[jj] : kh_[jj])) &
-                             ((W == 1) | (w1[jj] == kl_[jj]));
-            const uint32_t bh = (uint32_t)(__ballot(valid && hit) >> ql4) & 0xFu;
-            const uint32_t be = (uint32_t)(__ballot(valid && empty) >> ql4) & 0xFu;
-            const uint32_t fh = bh ? (uint32_t)__builtin_ctz(bh) : 4u;
-            const uint32_t fe = be ? (uint32_t)__builtin_ctz(be) : 4u;
-            // hit slot: ext | found flag | head-record index << 7
-            const uint32_t ext =
-                qor32(q4 == fh ? (slot_ext(w0[jj]) | 0x40u | ((chains ? slot_hidx(w0[jj], p) : 0u) << 7)) : 0u);
-            if (q4 == (uint32_t)jj) {
-                myfh = fh;
-                myfe = fe;
-                myext = ext;
-                r0 = w0[jj];
-                r1 = w1[jj];
-            }
-        }
+        const QuadProbe pr =
+            quad_probe<W>((active && probing) ? s : WQ_IDLE, k, slots, cap, mw.headrec, p, chains, q, ql);
         if (active && probing) {
             if (s & WQ_REC) {
                 // head record: jump to the run's tail, appending the bases of its links
-                k = slot_key(r0, r1, p);
-                st = ext_fwd(slot_ext(r0));
-                nsucc = rec_succ(r0, p);
-                uint32_t n = rec_links(r0, p);  // links: the last n bases of the tail key
+                k = slot_key(pr.r0, pr.r1, p);
+                st = ext_fwd(slot_ext(pr.r0));
+                nsucc = rec_succ(pr.r0, p);
+                uint32_t n = rec_links(pr.r0, p);  // links: the last n bases of the tail key
                 while (n) {
                     const uint32_t room = 32u - (steps & 31u), m = n < room ? n : room;
-                    const int sh = 2 * (int)(n - m);  // bits [sh, sh + 2m) of V, oldest base first
-                    const uint64_t x = sh < 62 ? (k.lo >> sh) | (k.hi << (62 - sh)) : k.hi >> (sh - 62);
-                    const uint64_t v = m >= 32 ? x : x & ((1ull << (2 * m)) - 1);
-                    const uint64_t r = ((uint64_t)__builtin_bitreverse32((uint32_t)v) << 32) |
-                                       __builtin_bitreverse32((uint32_t)(v >> 32));
-                    const uint64_t rev = ((r >> 1) & 0x5555555555555555ull) | ((r & 0x5555555555555555ull) << 1);
-                    put(rev >> (64 - 2 * m), m, buf, steps, nrec, nwords, rec, origin, idx);
+                    put(key_tail_piece(k, n, m), m, buf, steps, nrec, nwords, rec, origin, idx);
                     n -= m;
                 }
                 probing = false;
-            } else if (myfh < myfe) {
-                const uint32_t hidx = myext >> 7, tf = ext_fwd(myext & 63u);
+            } else if (pr.fh < pr.fe) {
+                const uint32_t hidx = pr.ext >> 7, tf = ext_fwd(pr.ext & 63u);
                 // a start walks from its own record (kmer_hash.cpp:42-44): a record whose run
                 // begins with another extension (a duplicate key) is not used for it
                 if (hidx && !(entry && tf != efwd) && nwords + 3 <= MW_RUN_WORDS) {  // the run's <= 2 words fit
@@ -286,7 +225,7 @@ __global__ __launch_bounds__(BLOCK) void k_mw_run(KParams p_in, const uint64_t* 
                     probing = false;
                 }
                 entry = false;
-            } else if (myfe < 4u || ++pb > pb_max) {
+            } else if (pr.fe < 4u || ++pb > pb_max) {
                 if (entry) {  // a start k-mer need not be in this shard (kh_set_starts): step from its own
                     st = efwd;
                     probing = false;
@@ -446,10 +385,9 @@ hipError_t launch_mw_run(const KParams& p, TableView t, const MWalkRound& mw, un
     // ~4 inputs per lane keeps lanes busy through the run-length tail without a work queue
     constexpr uint64_t ipl = 4;
     const unsigned g = grid_for((mw.n_in + ipl - 1) / ipl, 4096);
-    if (p.W == 1)
-        with_kt<1>(p.K, [&](auto kt) { k_mw_run<1, decltype(kt)::value><<<g, BLOCK, 0, s>>>(p, t.slots, t.cap, mw, stats); });
-    else
-        with_kt<2>(p.K, [&](auto kt) { k_mw_run<2, decltype(kt)::value><<<g, BLOCK, 0, s>>>(p, t.slots, t.cap, mw, stats); });
+    with_wkt(p, [&](auto w, auto kt) {
+        k_mw_run<decltype(w)::value, decltype(kt)::value><<<g, BLOCK, 0, s>>>(p, t.slots, t.cap, mw, stats);
+    });
     return hipGetLastError();
 }
 

@@ -3,6 +3,7 @@ host codec vs the reference KATs, text packing vs the oracle, and the synthetic 
 import hashlib
 import json
 import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -68,6 +69,16 @@ def test_pack_every_byte_value():
         else:
             with pytest.raises(kh.KmerHashError):
                 kh.pack_kmer(19, s)
+
+
+def test_key_tail_piece_matches_per_base_loop():
+    """kh_codec.hpp key_tail_piece (the bases a chain record's tail key carries, as both walkers
+    append them) against a per-base loop: tests/cpp/test_key_tail.cpp, k = 19 / 31 / 51 / 60, every
+    n and every first-piece length m, 64 random keys per k."""
+    exe = os.path.join(os.path.dirname(GOLDEN), "cpp", "test_key_tail")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.startswith("key_tail ok ")
 
 
 @pytest.mark.parametrize("name", sorted(MANIFEST))
