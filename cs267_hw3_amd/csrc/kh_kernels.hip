@@ -367,9 +367,21 @@ __global__ __launch_bounds__(BLOCK) void k_walk_q(KParams p_in, const uint64_t* 
                                 long_known = __hip_atomic_load(wb.seg_long, __ATOMIC_RELAXED,
                                                                __HIP_MEMORY_SCOPE_AGENT) != 0;
                                 if (!long_known) {  // defer every splitter walker to phase 1
-                                    if (lane == 0 && atomicMax(&ctr[CT_WALK_NEXT], (unsigned long long)n_all) < n_all)
-                                        __hip_atomic_store(wb.seg_long + 1, 1u, __ATOMIC_RELAXED,
-                                                           __HIP_MEMORY_SCOPE_AGENT);
+                                    // The flag whatever the queue head was: this reservation holds
+                                    // splitter walkers and may itself reach n_all (a queue that one
+                                    // reservation ends: the head then already stands at or past n_all).
+                                    if (lane == 0) {
+                                        const unsigned long long head =
+                                            atomicMax(&ctr[CT_WALK_NEXT], (unsigned long long)n_all);
+                                        // always true (the head never is ~0): it only keeps the store
+                                        // behind the atomic's return, as before. A store that does not
+                                        // wait took 2 more VGPRs in every instantiation with ROCm 7's
+                                        // compiler (<2,0>: 98, a wave of occupancy less); drop the
+                                        // test if a later toolchain no longer shows that.
+                                        if (head != ~0ull)
+                                            __hip_atomic_store(wb.seg_long + 1, 1u, __ATOMIC_RELAXED,
+                                                               __HIP_MEMORY_SCOPE_AGENT);
+                                    }
                                     n = wb.n_starts;
                                 }
                             }
@@ -1323,7 +1335,14 @@ __global__ __launch_bounds__(BLOCK) void k_seg_chain(WalkBuffers wb, SegBuffers 
                 if (atomicExch(&sb.seg_contig[g], (uint32_t)c) != SEG_NONE) atomicAdd(&stats[ST_CHUNK_OVF], 1ull);
                 sb.seg_off[g] = (uint32_t)off;
             }
-            off += wb.contig_len[g] - 1;
+            // a linked splitter segment no walker walked (deferred and lost): no length to add;
+            // counted as an overlap, so kh_assemble redoes the walk unsegmented
+            const uint32_t len = wb.contig_len[g];
+            if (len == 0) {
+                atomicAdd(&stats[ST_CHUNK_OVF], 1ull);
+                break;
+            }
+            off += len - 1;
             g = wb.seg_next[g];
             if (g == SEG_NONE) break;
             if (++hops > nseg || off > wb.max_steps) {  // segments in a cycle
@@ -1350,7 +1369,9 @@ __global__ __launch_bounds__(BLOCK) void k_seg_jump(WalkBuffers wb, SegBuffers s
          i += (uint64_t)gridDim.x * BLOCK) {
         uint32_t g = (uint32_t)i, sum = 0;
         for (uint32_t h = 0; h < SEG_JUMP && g != SEG_NONE; ++h) {
-            sum += wb.contig_len[g] - 1;
+            const uint32_t len = wb.contig_len[g];
+            if (len == 0) break;  // not walked (k_seg_chain reports it where a contig links to it)
+            sum += len - 1;
             g = wb.seg_next[g];
         }
         sb.jump[i] = g;
@@ -1392,7 +1413,9 @@ __global__ __launch_bounds__(BLOCK) void k_seg_fill(WalkBuffers wb, SegBuffers s
         const uint32_t c = sb.seg_contig[g];
         uint64_t off = sb.seg_off[g];
         for (uint32_t h = 1; h < SEG_JUMP; ++h) {
-            off += wb.contig_len[g] - 1;
+            const uint32_t len = wb.contig_len[g];
+            if (len == 0) break;  // not walked: nothing follows it
+            off += len - 1;
             g = wb.seg_next[g];
             if (g == SEG_NONE) break;
             if (atomicExch(&sb.seg_contig[g], c) != SEG_NONE) atomicAdd(&stats[ST_CHUNK_OVF], 1ull);
@@ -1498,6 +1521,7 @@ __global__ __launch_bounds__(BLOCK) void k_write_chunks_seg(int K, const uint64_
         const uint32_t c = own ? g : seg_contig[g];
         if (c == SEG_NONE) continue;  // a segment no contig reached
         const uint64_t cb = ch < nseg ? 0ull : (uint64_t)seq[ch] * CHUNK_BASES;
+        if (seg_len[g] == 0) continue;  // a segment no walker walked
         const uint64_t app = (uint64_t)seg_len[g] - 1;
         if (cb + 32 * q >= app) continue;
         const uint32_t cnt = (uint32_t)min<uint64_t>(CHUNK_BASES, app - cb);

@@ -245,3 +245,22 @@ def test_sharded_short_walk_first(P, n_long):
         check_ranks(g, t, P)
     assert all(v == bool(n_long) for v in info["segmented"].values())
 
+
+
+@pytest.mark.parametrize("P", [1, 2, 3])
+@pytest.mark.parametrize("shape", ["A", "B"])
+@pytest.mark.parametrize("k", [19, 31, 51])
+def test_sharded_tiny_deferred_shapes(k, shape, P):
+    """The one-reservation inputs of test_gpu_small.py (30 / 90 contigs of 2-8 k-mers plus one of
+    120: 262-586 k-mers in all) over P logical ranks: the short walk first, abandoned for the
+    segmented walk when the long contig shows, at a few hundred walkers per rank instead of
+    test_sharded_short_walk_first's 1.5M k-mers. The ranks' lines together are the oracle's."""
+    from cases import contigs_truth, deferred_case
+    from cs267_hw3_amd.dist import run_threaded
+    text, contigs, f = deferred_case(k, shape)
+    recs = kh.pack_text(k, text)
+    rc, want, nc, _, _, _ = ob.assemble(k, recs)
+    assert rc == 0 and nc == f["ns"] and want == contigs_truth(contigs)
+    texts = run_threaded(k, recs, P)
+    assert sorted(b"".join(texts).splitlines()) == sorted(want.splitlines())
+    assert sum(len(t) for t in texts) == len(want)

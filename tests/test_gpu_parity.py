@@ -9,7 +9,7 @@ import pytest
 import cs267_hw3_amd as kh
 from cs267_hw3_amd import _lib
 import oracle_bind as ob
-from cases import merging_walks_text
+from cases import merging_walks_text, split_hash as _split_hash
 
 pytestmark = pytest.mark.gpu
 
@@ -130,15 +130,6 @@ def test_overlapping_walks_redo(k, L, every):
     dirty_device_memory()
     _, got, got_nc = run(k, recs)
     assert got_nc == nc and got == want
-
-
-def _split_hash(kmer):
-    """kh_codec.hpp split_hash of a k-mer string (V = 2-bit bases, first base most significant)."""
-    v = 0
-    for ch in kmer:
-        v = (v << 2) | "ACGT".index(ch)
-    lo = v & ((1 << 62) - 1)
-    return (((lo & 0xFFFFFFFF) ^ (lo >> 32)) * 0x9E3779B1) & 0xFFFFFFFF
 
 
 @pytest.mark.parametrize("k", [19, 51])

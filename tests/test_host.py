@@ -75,7 +75,11 @@ def test_key_tail_piece_matches_per_base_loop():
     """kh_codec.hpp key_tail_piece (the bases a chain record's tail key carries, as both walkers
     append them) against a per-base loop: tests/cpp/test_key_tail.cpp, k = 19 / 31 / 51 / 60, every
     n and every first-piece length m, 64 random keys per k."""
-    exe = os.path.join(os.path.dirname(GOLDEN), "cpp", "test_key_tail")
+    cpp = os.path.join(os.path.dirname(GOLDEN), "cpp")
+    exe = os.path.join(cpp, "test_key_tail")
+    # (built with the other C++ tests; on its own it needs only g++, and make rebuilds it when
+    # kh_codec.hpp changed)
+    subprocess.run(["make", "-s", "-C", cpp, exe], check=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.startswith("key_tail ok ")
