@@ -120,6 +120,7 @@ struct kh_table {
     DevBuf stage2, stage3;
     DevBuf contig_len, contig_off, chunk_data, chunk_owner, chunk_seq, text, line_first;
     DevBuf route_hist, route_off, route_scratch, route_own;                       // sharded path
+    DevBuf find_own, find_ext;                // batched find: owners of routed keys / answers in key order
     DevBuf pb_buf1, pb_buf2, pb_cnt, pb_ovf;  // partitioned build
     DevBuf headrec;                           // chain head records (region build -> walker)
     DevBuf hot;                               // remapped-region bitmap (KParams::hot), 2 levels of HOT_WORDS
@@ -445,7 +446,7 @@ int kh_destroy(kh_table* t) {
                       &t->ms_jump, &t->ms_acc, &t->ms_stab, &t->ms_stab_id, &t->ms_qsrc, &t->ms_misc,
                       &t->mw_cnt, &t->mw_list, &t->mw_carry[0], &t->mw_carry[1], &t->mw_carry_dst[0],
                       &t->mw_carry_dst[1], &t->ms_res[0], &t->ms_res[1], &t->ms_res[2], &t->ms_res[3], &t->ms_res[4],
-                      &t->ms_res[5], &t->ms_pend, &t->route_spl,
+                      &t->ms_res[5], &t->ms_pend, &t->route_spl, &t->find_own, &t->find_ext,
                       &t->pb_buf1, &t->pb_buf2, &t->pb_cnt, &t->pb_ovf, &t->headrec, &t->hot, &t->rbounds};
     if (t->side) (void)hipStreamSynchronize(t->side);  // k_rec_succ may still read the table
     for (auto* b : bufs) b->release();
@@ -1186,6 +1187,55 @@ int kh_route_dev(kh_table* t, const void* dev_recs, uint64_t n, int nranks, void
                             t->route_hist.as<uint64_t>(), t->route_off.as<uint64_t>(),
                             t->route_scratch.as<uint64_t>(), t->route_own.as<uint32_t>(), (uint64_t*)words_out,
                             (uint64_t*)counts_out, t->stream));
+    return KH_OK;
+}
+
+// ---- batched find across shards (kh_find.hip): route keys by owner, answer, reorder -------------
+int kh_find_route_dev(kh_table* t, const void* dev_keys, uint64_t n, int nranks, void* dev_keys_out,
+                      void* dev_index_out, void* dev_counts_out) {
+    if (!t) return fail(KH_ERR_ARG, "null table");
+    if (nranks < 1 || nranks > kh::MAX_RANKS) return fail(KH_ERR_ARG, "nranks %d outside [1,%d]", nranks, kh::MAX_RANKS);
+    if (n >> 32) return fail(KH_ERR_ARG, "%llu keys in one batch (positions are 32-bit)", (unsigned long long)n);
+    if (t->staging) return fail(KH_ERR_STATE, "a staged insert is open (kh_insert_words_finish first)");
+    if (n == 0) return KH_OK;
+    if (!dev_keys || !dev_keys_out || !dev_index_out || !dev_counts_out) return fail(KH_ERR_ARG, "null buffer");
+    if ((uintptr_t)dev_index_out & 3u) return fail(KH_ERR_ARG, "positions must be 4-byte aligned");
+    if ((uintptr_t)dev_counts_out & 7u) return fail(KH_ERR_ARG, "counts must be 8-byte aligned");
+    if (int rc = set_device(t)) return rc;
+    if (int rc = ensure_route(t, n, nranks)) return rc;
+    if (int rc = t->find_own.ensure((n + 16) * 4)) return rc;
+    KH_HIP(kh::launch_find_route(t->kp, (const uint8_t*)dev_keys, n, (uint32_t)nranks, t->route_hist.as<uint64_t>(),
+                                 t->route_off.as<uint64_t>(), t->route_scratch.as<uint64_t>(),
+                                 t->find_own.as<uint32_t>(), (uint8_t*)dev_keys_out, (uint32_t*)dev_index_out,
+                                 (uint64_t*)dev_counts_out, t->stream));
+    return KH_OK;
+}
+
+int kh_find_answer_dev(kh_table* t, const void* dev_keys, uint64_t m, void* dev_ext_out) {
+    if (!t) return fail(KH_ERR_ARG, "null table");
+    if (t->staging) return fail(KH_ERR_STATE, "a staged insert is open (kh_insert_words_finish first)");
+    if (m == 0) return KH_OK;
+    if (!dev_keys || !dev_ext_out) return fail(KH_ERR_ARG, "null buffer");
+    if (int rc = set_device(t)) return rc;
+    if (int rc = clean_slots(t)) return rc;
+    KH_HIP(kh::launch_find_answer(t->kp, (const uint8_t*)dev_keys, m, view(t), (uint8_t*)dev_ext_out, t->stream));
+    return KH_OK;
+}
+
+int kh_find_gather_dev(kh_table* t, const void* dev_keys, uint64_t n, const void* dev_index,
+                       const void* dev_ext_grouped, void* dev_recs_out, void* dev_found_out) {
+    if (!t) return fail(KH_ERR_ARG, "null table");
+    if (n >> 32) return fail(KH_ERR_ARG, "%llu keys in one batch (positions are 32-bit)", (unsigned long long)n);
+    if (t->staging) return fail(KH_ERR_STATE, "a staged insert is open (kh_insert_words_finish first)");
+    if (n == 0) return KH_OK;
+    if (!dev_keys || !dev_index || !dev_ext_grouped || !dev_recs_out || !dev_found_out)
+        return fail(KH_ERR_ARG, "null buffer");
+    if ((uintptr_t)dev_index & 3u) return fail(KH_ERR_ARG, "positions must be 4-byte aligned");
+    if (int rc = set_device(t)) return rc;
+    if (int rc = t->find_ext.ensure((n + 16) * 2)) return rc;
+    KH_HIP(kh::launch_find_gather(t->kp, (const uint8_t*)dev_keys, n, (const uint32_t*)dev_index,
+                                  (const uint8_t*)dev_ext_grouped, t->find_ext.as<uint16_t>(), (uint8_t*)dev_recs_out,
+                                  (uint8_t*)dev_found_out, t->stream));
     return KH_OK;
 }
 

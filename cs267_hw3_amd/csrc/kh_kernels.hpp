@@ -358,6 +358,21 @@ hipError_t launch_route(const KParams& p, const uint8_t* recs, uint64_t n, uint3
 hipError_t launch_insert_words(const KParams& p, const uint64_t* words, uint64_t m, TableView t,
                                unsigned long long* stats, hipStream_t s);
 
+// Batched find across shards (kh_find.hip). Route: n PACKED-byte keys -> the keys grouped by owner
+// rank, the original position of each grouped key, counts (nranks + 1 words, last = n); hist / off /
+// scratch as launch_route, own: n words.
+hipError_t launch_find_route(const KParams& p, const uint8_t* keys, uint64_t n, uint32_t nranks, uint64_t* hist,
+                             uint64_t* off, uint64_t* scratch, uint32_t* own, uint8_t* keys_out, uint32_t* index_out,
+                             uint64_t* counts, hipStream_t s);
+// Answer: m keys -> 2 bytes each {backward, forward} chars, {0,0} = not in the table.
+hipError_t launch_find_answer(const KParams& p, const uint8_t* keys, uint64_t m, TableView t, uint8_t* ext_out,
+                              hipStream_t s);
+// Gather: answers in grouped order + index -> records and found flags in the order of keys
+// (launch_find's bytes); ext_orig: n 16-bit words of scratch.
+hipError_t launch_find_gather(const KParams& p, const uint8_t* keys, uint64_t n, const uint32_t* index,
+                              const uint8_t* ext_grouped, uint16_t* ext_orig, uint8_t* recs_out, uint8_t* found_out,
+                              hipStream_t s);
+
 }  // namespace kh
 
 // ---- partitioned (atomic-free) bulk build ------------------------------------------------------

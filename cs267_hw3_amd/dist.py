@@ -411,6 +411,37 @@ class GpuShard:
         check(self.L.kh_host_syncs(self.h, ctypes.byref(v)))
         return v.value
 
+    # batched find across shards (kh_find.hip): keys are uint8 [n, PACKED] device tensors
+    def find_route(self, keys, nranks):
+        """Keys -> (the keys grouped by owner rank [n, PACKED], int32 [n]: the position in `keys` of
+        grouped key j, int64 [P+1] counts: per owner, then n) (kh_find_route_dev)."""
+        n = keys.shape[0]
+        out = torch.empty((max(n, 1), keys.shape[1]), dtype=torch.uint8, device=self.dev)
+        index = self.zeros(n, torch.int32)
+        counts = self.zeros(nranks + 1, torch.int64)
+        if n == 0:
+            counts.zero_()  # the call writes nothing for an empty batch
+        check(self.L.kh_find_route_dev(self.h, self._p(keys), n, nranks, self._p(out), self._p(index),
+                                       self._p(counts)))
+        return out, index, counts
+
+    def find_answer(self, keys, m):
+        """m keys this shard owns -> uint8 [m, 2] {backward, forward} chars, {0, 0} = absent
+        (kh_find_answer_dev)."""
+        ext = torch.empty((max(int(m), 1), 2), dtype=torch.uint8, device=self.dev)
+        check(self.L.kh_find_answer_dev(self.h, self._p(keys), int(m), self._p(ext)))
+        return ext
+
+    def find_gather(self, keys, index, ext):
+        """The caller's keys, find_route's index and the answers in grouped order -> (records
+        uint8 [n, R], found uint8 [n]) in the order of `keys` (kh_find_gather_dev)."""
+        n = keys.shape[0]
+        recs = torch.empty((max(n, 1), self.R), dtype=torch.uint8, device=self.dev)
+        found = self.zeros(n, torch.uint8)
+        check(self.L.kh_find_gather_dev(self.h, self._p(keys), n, self._p(index), self._p(ext), self._p(recs),
+                                        self._p(found)))
+        return recs[:n], found[:n]
+
     # migrating-walker rounds (fixed-size exchange slots: no device read per round)
     MSG_WORDS = _lib.MSG_WORDS
     TEXT_REC_WORDS = _lib.TEXT_REC_WORDS
@@ -508,6 +539,8 @@ class DistributedKmerHashMap:
                       collective (hash_map.hpp:55-80 ends in a barrier too).
     assemble(total):  walk this rank's start k-mers; returns this rank's contig text
                       (= test_<rank>.dat bytes); collective.
+    find(keys):       hash_map.hpp:83-107 for a batch of keys, any key from any rank: (records,
+                      found) in the caller's key order; collective.
     """
 
     def __init__(self, comm, shard):
@@ -526,6 +559,7 @@ class DistributedKmerHashMap:
         self.timer = None       # a PhaseTimer: per-phase stream time of the step (bench)
         self.xbytes = 0         # bytes this rank sent to other ranks in the step (all exchanges)
         self.text_records = self.seg_records = 0  # text / retag records received by the last walk
+        self.find_key_bytes = self.find_answer_bytes = 0  # bytes the last find put into its two exchanges
 
     # tests: stall this rank when it begins phase HANG_AT[0] (HANG_AT[1] = the rank) — a rank that
     # never reaches the next collective, as a crashed or diverged peer would look to the others
@@ -802,6 +836,65 @@ class DistributedKmerHashMap:
             self._begin("build")
             sh.finish_words()
         return m
+
+    # every phase name find() uses, in order
+    FIND_PHASES = ("find_route", "find_exchange", "find_answer", "find_return", "find_gather")
+
+    def find(self, keys):
+        """hash_map.hpp:83-107 find for a batch of keys, any key from any rank (collective: every
+        rank calls it; its own n may be 0 and differ between ranks). keys: pkmer_t rows, a device
+        uint8 tensor [n, PACKED] -> (records uint8 [n, R], found uint8 [n]) device tensors; or a
+        host numpy array (uploaded, and the results come back as numpy: records, found bool, as
+        KmerHashTable.find gives them). An absent key: a zeroed record and found = 0.
+
+        Keys are grouped by owner and exchanged (PACKED bytes per key), each owner answers what it
+        received with 2 bytes per key, the answers go back through the same exchange with the
+        splits swapped, and the asker puts them in its key order. One blocking host read (the
+        counts). Legal after insert_all, before and after assemble; changes nothing either reads."""
+        sh, P = self.shard, self.P
+        kp = (sh.k + 3) // 4
+        host = not torch.is_tensor(keys)
+        if host:
+            import numpy as np
+            keys = torch.from_numpy(np.ascontiguousarray(keys, dtype=np.uint8).reshape(-1, kp))
+            if getattr(sh, "dev", None) is not None:
+                keys = keys.to(sh.dev)
+        n = keys.numel() // kp
+        keys = keys.contiguous().view(n, kp)
+        exchange = P > 1 or self.SELF_EXCHANGE
+        resume = self._cur  # a step's open phase (insert_all leaves its last one open for the timer)
+        self._begin("find_route")
+        gkeys, index, counts = sh.find_route(keys, P)
+        send, recv, _, gmax, _ = self._exchange_counts(counts)
+        m = sum(recv)
+        self.find_key_bytes = self.find_answer_bytes = 0  # what this rank put into the two exchanges
+        if exchange:
+            self._begin("find_exchange")
+            rkeys = torch.empty((max(m, 1), kp), dtype=torch.uint8, device=keys.device)
+            self.find_key_bytes = n * kp
+            self._all_to_all(rkeys.view(-1)[:m * kp], gkeys.view(-1)[:n * kp], [c * kp for c in recv],
+                             [c * kp for c in send], gmax * kp)
+        else:
+            rkeys = gkeys
+        self._begin("find_answer")
+        ext = sh.find_answer(rkeys, m)
+        if exchange:
+            self._begin("find_return")
+            back = torch.empty((max(n, 1), 2), dtype=torch.uint8, device=keys.device)
+            self.find_answer_bytes = m * 2
+            self._all_to_all(back.view(-1)[:n * 2], ext.view(-1)[:m * 2], [c * 2 for c in send],
+                             [c * 2 for c in recv], gmax * 2)
+        else:
+            back = ext
+        self._begin("find_gather")
+        recs, found = sh.find_gather(keys, index, back)
+        if resume is not None:
+            self._begin(resume)
+        else:
+            self._end()
+        if host:
+            return recs.cpu().numpy(), found.cpu().numpy().astype(bool)
+        return recs, found
 
     def assemble(self, total_kmers):
         """Walk this rank's start k-mers (collective); returns the number of rounds. Walks that

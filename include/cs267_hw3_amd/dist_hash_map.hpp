@@ -25,6 +25,9 @@
 //               own, answers gathered), and barrier()/process_requests() keep answering rounds until
 //               every rank has reached them -- the UPC++ progress the reference's barrier makes
 //               (kmer_hash.cpp:136, hash_map.hpp:110-113) while other ranks still walk
+//   find_all    a batch of keys from every rank at once: grouped by owner on the GPU, one all-to-all
+//               of the keys, 2-byte answers back through the same exchange reversed, put in key
+//               order on the GPU (kh_find_route_dev / kh_find_answer_dev / kh_find_gather_dev)
 //
 // The same protocol has a Python host in cs267_hw3_amd/dist.py (torch.distributed).
 #pragma once
@@ -151,7 +154,8 @@ public:
         (void)hipSetDevice(device_);
         if (t_) kh_destroy(t_);
         for (auto* b : {&words_, &recv_, &counts_, &tout_, &trecv_, &lout_, &lin_, &qout_, &qin_, &sout_, &sin_,
-                        &recs_, &pack_, &gather_, &live_, &slots_[0], &slots_[1], &recv_slots_[0], &recv_slots_[1]})
+                        &recs_, &pack_, &gather_, &live_, &slots_[0], &slots_[1], &recv_slots_[0], &recv_slots_[1],
+                        &fkeys_, &fgroup_, &findex_, &fext_, &fpack_, &frecv_, &fans_, &fback_, &frecs_})
             b->release();
         for (auto e : events_) (void)hipEventDestroy(e);
         if (stream_) (void)hipStreamDestroy(stream_);
@@ -473,6 +477,71 @@ public:
         return found != 0;
     }
 
+    // Batched find (hash_map.hpp:83-107 for n keys at once, any key from any rank). Collective:
+    // every rank calls it, with its own n (0 allowed). keys: n pkmer_t keys; recs_out: n kmer_pair
+    // records (an absent key: zeroed), found: n bytes 0/1 -- what kh_find gives on one table holding
+    // every k-mer. With or without a peer group: the keys are grouped by owner on the GPU
+    // (kh_find_route_dev), exchanged through the communicator's alltoallv, answered by their owners
+    // with 2 bytes per key (kh_find_answer_dev), and the answers go back through the same exchange
+    // reversed (kh_find_gather_dev puts them in key order). The transport moves 64-bit words, so each
+    // peer's block is padded to whole words (at most 7 bytes per peer and direction). One blocking
+    // read of the counts, one of the results.
+    void find_all(const uint8_t* keys, uint64_t n, uint8_t* recs_out, uint8_t* found) {
+        hip_check(hipSetDevice(device_), "hipSetDevice");
+        const uint64_t P = (uint64_t)P_, Pk = (uint64_t)((k_ + 3) / 4);
+        auto words_of = [](uint64_t bytes) { return (bytes + 7) / 8; };
+        uint8_t* dk = static_cast<uint8_t*>(fkeys_.ensure(n * Pk + 16));
+        uint8_t* gk = static_cast<uint8_t*>(fgroup_.ensure(n * Pk + 16));
+        void* idx = findex_.ensure(n * 4 + 16);
+        uint8_t* grouped_ext = static_cast<uint8_t*>(fext_.ensure(n * 2 + 16));
+        int64_t* cnt = counts_.words(P + 1);
+        if (n) {
+            hip_check(hipMemcpyAsync(dk, keys, n * Pk, hipMemcpyHostToDevice, stream_), "hipMemcpyAsync");
+            abi_check(kh_find_route_dev(t_, dk, n, P_, gk, idx, cnt));
+        } else {
+            hip_check(hipMemsetAsync(cnt, 0, (P + 1) * 8, stream_), "hipMemsetAsync");  // the route writes nothing
+        }
+        if (P == 1) {  // every key is this shard's: nothing moves
+            abi_check(kh_find_answer_dev(t_, gk, n, grouped_ext));
+        } else {
+            Exchange ex;
+            exchange_counts(ex);
+            std::vector<uint64_t> sc(P), sd(P), rc(P), rd(P), ac(P), ad(P), bc(P), bd(P), goff(P);
+            uint64_t so = 0, ro = 0, ao = 0, bo = 0, go = 0;
+            for (uint64_t q = 0; q < P; ++q) {
+                sc[q] = words_of(ex.send[q] * Pk), sd[q] = so, so += sc[q];  // keys out
+                rc[q] = words_of(ex.recv[q] * Pk), rd[q] = ro, ro += rc[q];  // keys in
+                ac[q] = words_of(ex.recv[q] * 2), ad[q] = ao, ao += ac[q];   // answers out
+                bc[q] = words_of(ex.send[q] * 2), bd[q] = bo, bo += bc[q];   // answers in
+                goff[q] = go, go += ex.send[q];
+            }
+            int64_t* pack = fpack_.words(std::max<uint64_t>(so, 1));
+            for (uint64_t q = 0; q < P; ++q)
+                if (ex.send[q])
+                    hip_check(hipMemcpyAsync(pack + sd[q], gk + goff[q] * Pk, ex.send[q] * Pk, hipMemcpyDeviceToDevice,
+                                             stream_), "hipMemcpyAsync");
+            int64_t* rkeys = frecv_.words(std::max<uint64_t>(ro, 1));
+            comm_.alltoallv(pack, sc.data(), sd.data(), rkeys, rc.data(), rd.data(), words_of(ex.gmax * Pk), stream_);
+            int64_t* ans = fans_.words(std::max<uint64_t>(ao, 1));
+            for (uint64_t q = 0; q < P; ++q)
+                abi_check(kh_find_answer_dev(t_, rkeys + rd[q], ex.recv[q], ans + ad[q]));
+            int64_t* back = fback_.words(std::max<uint64_t>(bo, 1));
+            comm_.alltoallv(ans, ac.data(), ad.data(), back, bc.data(), bd.data(), words_of(ex.gmax * 2), stream_);
+            for (uint64_t q = 0; q < P; ++q)
+                if (ex.send[q])
+                    hip_check(hipMemcpyAsync(grouped_ext + goff[q] * 2, back + bd[q], ex.send[q] * 2,
+                                             hipMemcpyDeviceToDevice, stream_), "hipMemcpyAsync");
+        }
+        if (!n) return;
+        uint8_t* dr = static_cast<uint8_t*>(frecs_.ensure(n * R_ + n + 32));
+        uint8_t* df = dr + n * R_;
+        abi_check(kh_find_gather_dev(t_, dk, n, idx, grouped_ext, dr, df));
+        hip_check(hipMemcpyAsync(recs_out, dr, n * R_, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync");
+        hip_check(hipMemcpyAsync(found, df, n, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync");
+        hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        ++syncs_;
+    }
+
     // hash_map.hpp:110-113 process_requests (progress + barrier) / upcxx::barrier(): collective.
     // Without a peer group it answers find rounds until every rank has arrived here.
     void barrier() {
@@ -704,6 +773,7 @@ private:
     std::vector<hipEvent_t> events_;
     DevBuf words_, recv_, counts_, tout_, trecv_, lout_, lin_, qout_, qin_, sout_, sin_, recs_, pack_, gather_, live_;
     DevBuf slots_[2], recv_slots_[2];
+    DevBuf fkeys_, fgroup_, findex_, fext_, fpack_, frecv_, fans_, fback_, frecs_;  // find_all
 };
 
 }  // namespace kh

@@ -173,6 +173,35 @@ int kh_counters_dev(kh_table* t, void* dev_out);
  * made beside the region build, so the read waits for the start / splitter compaction, not for the
  * build (the one-rank sharded step reads them without idling the device). */
 int kh_counters(kh_table* t, uint64_t* out2);
+/* Batched find across shards: DistributedHashMap::find (hash_map.hpp:83-107) for a whole batch of
+ * keys from any rank, instead of one blocking RPC per key (hash_map.hpp:94-100). The asker groups
+ * its keys by owner, the caller exchanges them, every owner answers the keys it received with 2
+ * bytes each, the caller sends the answers back (the same exchange with the splits swapped) and the
+ * asker puts them in its own key order:
+ *   route(keys) -> exchange of counts, then of keys_out (PACKED B per key)
+ *   answer(received keys) -> exchange back (2 B per key, not a record: the asker has the key)
+ *   gather(keys, index, answers as they came back) -> records + found flags
+ * All three are async on the table's stream and change neither the table, the start list nor a
+ * walk. n = 0 / m = 0: KH_OK, nothing is done or written. n >= 2^32, nranks outside [1, 64] or a
+ * null buffer: KH_ERR_ARG. A staged insert left open (kh_insert_words_stage_dev without finish):
+ * KH_ERR_STATE. Key, record, answer and flag buffers may have any alignment.
+ *
+ * kh_find_route_dev: n pkmer_t keys (contiguous) -> dev_keys_out: the same n keys, owner 0's first,
+ * then owner 1's, ... (order inside a group unspecified); dev_index_out: uint32[n], the position in
+ * dev_keys of grouped key j; dev_counts_out: uint64[nranks + 1], the keys per owner, then n. The
+ * owner of a key is kh_key_owner(t, key, nranks). */
+int kh_find_route_dev(kh_table* t, const void* dev_keys, uint64_t n, int nranks, void* dev_keys_out,
+                      void* dev_index_out, void* dev_counts_out);
+/* m keys -> dev_ext_out: 2 bytes per key, the {backward, forward} extension chars of the key's
+ * record in this table, {0, 0} when the table does not hold the key (an empty or cleared table
+ * answers {0, 0} for every key). */
+int kh_find_answer_dev(kh_table* t, const void* dev_keys, uint64_t m, void* dev_ext_out);
+/* dev_keys / dev_index: as given to / written by kh_find_route_dev; dev_ext_grouped: the answer of
+ * grouped key j at bytes 2j, 2j + 1 -> dev_recs_out: n kmer_pair records, dev_found_out: n bytes 0/1,
+ * in the order of dev_keys, byte for byte what kh_find_dev writes on one table holding every k-mer
+ * (an absent key: a zeroed record and 0). */
+int kh_find_gather_dev(kh_table* t, const void* dev_keys, uint64_t n, const void* dev_index,
+                       const void* dev_ext_grouped, void* dev_recs_out, void* dev_found_out);
 /* Migrating-walker rounds. The table is sharded by a hash of each k-mer's minimizer, so
  * consecutive k-mers of a contig mostly share an owner; a walker walks the local shard until its
  * next k-mer is owned elsewhere and is then sent there. Nothing below reads the device on the host:
