@@ -1,5 +1,33 @@
-"""Shared generators of edge-case inputs (test infrastructure; no GPU, no product imports)."""
+"""Shared generators of edge-case inputs and reference helpers (test infrastructure; no GPU, no
+product imports)."""
 import numpy as np
+
+
+class RecordDict:
+    """key bytes -> record of a record array [n, R] (sorted keys + binary search)."""
+
+    def __init__(self, k, recs):
+        self.KP = (k + 3) // 4
+        self.R = self.KP + 2
+        keys = self._s(recs[:, :self.KP])
+        order = np.argsort(keys, kind="stable")
+        self.keys, self.recs = keys[order], np.ascontiguousarray(recs[order])
+        assert len(np.unique(self.keys)) == len(self.keys)
+
+    def _s(self, a):  # rows as fixed-width byte strings (compared like memcmp)
+        return np.ascontiguousarray(a, dtype=np.uint8).view(f"S{self.KP}").ravel()
+
+    def lookup(self, q):
+        """-> (records [m, R] (zeroed where absent), found uint8 [m])"""
+        q = np.ascontiguousarray(q, dtype=np.uint8).reshape(-1, self.KP)
+        out = np.zeros((len(q), self.R), np.uint8)
+        if not len(q):
+            return out, np.zeros(0, np.uint8)
+        v = self._s(q)
+        i = np.minimum(np.searchsorted(self.keys, v), len(self.keys) - 1)
+        hit = self.keys[i] == v
+        out[hit] = self.recs[i[hit]]
+        return out, hit.astype(np.uint8)
 
 
 def merging_walks_text(k, L, seed, every=1):
@@ -68,11 +96,12 @@ def contigs_truth(contigs):
     return "".join(c + "\n" for c in contigs).encode()
 
 
+_BASE4 = str.maketrans("ACGT", "0123")
+
+
 def split_hash(kmer):
     """kh_codec.hpp split_hash of a k-mer string (V = 2-bit bases, first base most significant)."""
-    v = 0
-    for ch in kmer:
-        v = (v << 2) | "ACGT".index(ch)
+    v = int(kmer.translate(_BASE4), 4)
     lo = v & ((1 << 62) - 1)
     return (((lo & 0xFFFFFFFF) ^ (lo >> 32)) * 0x9E3779B1) & 0xFFFFFFFF
 
@@ -166,3 +195,102 @@ def short_lens(ns, seed, extra=0):
     contig that really stops at a splitter)."""
     rng = np.random.default_rng(seed)
     return [int(x) for x in rng.integers(1, 5, ns)] + ([extra] if extra else [])
+
+
+# ---- inputs of an exact record count for the sharded route kernels (test_gpu_route.py) ----------
+# One below / at / one above a wave (64), a block of the two-pass route (256), its tile
+# (ROUTE_TILE = 2048) and the tile of the one-pass route (REC_TILE = 3584), and two full tiles plus
+# one record.
+ROUTE_SIZES = (1, 63, 64, 65, 255, 256, 257, 2047, 2048, 2049, 3583, 3584, 3585, 7169)
+ROUTE_SEEDS = tuple(range(12))
+
+
+def route_lens(n, seed):
+    """Contig lengths (in k-mers) summing to exactly n: contigs of 1-4 k-mers and, one contig in
+    eight after the first two while they fit, one of 40-300: about one record in twenty is a
+    start, so the shuffled input has 64-record mask words with several starts and words with
+    none."""
+    rng = np.random.default_rng(seed)
+    lens, left = [], n
+    while left:
+        long = len(lens) >= 2 and rng.random() < 0.125
+        L = int(rng.integers(40, 301)) if long else int(rng.integers(1, 5))
+        L = min(L, left)
+        lens.append(L)
+        left -= L
+    assert sum(lens) == n
+    return lens
+
+
+def start_mask_words(k, text):
+    """The 64-record start-mask words of a fixed-width text: bit i of word w = record 64 w + i has
+    backward extension 'F' (kmer_hash.cpp:27-31)."""
+    n = len(text) // (k + 4)
+    words = [0] * ((n + 63) // 64)
+    for i in range(n):
+        if text[i * (k + 4) + k + 1] == ord("F"):
+            words[i >> 6] |= 1 << (i & 63)
+    return words
+
+
+def route_ok(n, words):
+    """Starts in the first and in the last mask word, a last word that is not full unless n is a
+    multiple of 64 (by construction), and from one two-pass tile on a mask word without starts."""
+    return bool(words[0]) and bool(words[-1]) and (n < 2047 or not all(words))
+
+
+def route_text(k, n):
+    """(text, contigs, seed) of exactly n k-mers: contigs_text of route_lens with one start record
+    moved to the first line and another to the last (they change places with the lines there), at
+    the first seed of ROUTE_SEEDS that satisfies route_ok; fails if none does. The contigs are in
+    the order of their start records, as contigs_text gives them."""
+    w = k + 4
+    for s in ROUTE_SEEDS:
+        seed = 7000 + 13 * k + n + s
+        text, contigs = contigs_text(k, route_lens(n, seed), seed)
+        lines = [text[i * w:(i + 1) * w] for i in range(n)]
+        at = [i for i in range(n) if lines[i][k + 1] == ord("F")]
+        lines[0], lines[at[0]] = lines[at[0]], lines[0]
+        if len(at) > 1:
+            j = at[-1] if at[-1] != 0 else at[0]  # (the line that was first now stands at at[0])
+            lines[n - 1], lines[j] = lines[j], lines[n - 1]
+        text = b"".join(lines)
+        by_start = {c[:k]: c for c in contigs}
+        contigs = [by_start[ln[:k].decode()] for ln in lines if ln[k + 1] == ord("F")]
+        if route_ok(n, start_mask_words(k, text)):
+            return text, contigs, seed
+    raise AssertionError(f"no seed gives the route input's preconditions at k={k}, n={n}")
+
+
+def chunk_bounds(n, calls, empty=None):
+    """Record bounds of `calls` successive route calls over n records: chunk starts at multiples of
+    16 records, as DistributedKmerHashMap.insert_all makes them (every chunk stays 16-B aligned);
+    `empty` = the index of a call that gets no record (not the last call: an empty chunk too starts
+    at a multiple of 16 records; the others split the records)."""
+    nch = calls - (empty is not None)
+    assert empty is None or 0 <= empty < nch
+    b = [min(n, (n * c // nch) & ~15) for c in range(nch)] + [n]
+    if empty is not None:
+        b.insert(empty, b[empty])
+    assert len(b) == calls + 1 and all(x % 16 == 0 for x in b[:-1]) and b == sorted(b)
+    return b
+
+
+def owned_subset_text(k, contigs, owner_of, keep_other, seed):
+    """A closed input whose k-mers nearly all share one owner: of `contigs`, those whose k-mers all
+    have the most frequent owner (owner_of(k-mer string) -> rank) plus every keep_other-th of the
+    rest, their lines shuffled. Returns (text, contigs in start-record order, hot owner)."""
+    own = [[owner_of(c[i:i + k]) for i in range(len(c) - k + 1)] for c in contigs]
+    flat = [q for o in own for q in o]
+    hot = max(set(flat), key=flat.count)
+    keep = [c for c, o in zip(contigs, own) if all(q == hot for q in o)]
+    keep += [c for c, o in zip(contigs, own) if any(q != hot for q in o)][::keep_other]
+    lines = []
+    for ci, c in enumerate(keep):
+        L = len(c) - k + 1
+        for i in range(L):
+            lines.append((c[i:i + k], "F" if i == 0 else c[i - 1], "F" if i == L - 1 else c[i + k],
+                          ci if i == 0 else -1))
+    perm = np.random.default_rng(seed).permutation(len(lines))
+    text = "".join(f"{lines[i][0]} {lines[i][1]}{lines[i][2]}\n" for i in perm).encode()
+    return text, [keep[lines[i][3]] for i in perm if lines[i][3] >= 0], hot

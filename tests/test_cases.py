@@ -1,6 +1,7 @@
 """The input builders of cases.py against the oracle (no GPU): the oracle's assembly of
 contigs_text(...) is the truth the builder returns, for the values of k and the length mixes the
-GPU tests of small inputs use (test_gpu_small.py, test_gpu_dist.py)."""
+GPU tests of small inputs use (test_gpu_small.py, test_gpu_dist.py, test_gpu_route.py)."""
+import numpy as np
 import pytest
 
 import cases
@@ -97,3 +98,80 @@ def test_split_hash_mirror():
     c = "ACGT" * 5
     assert cases.walk_splitter_indices(4, c, 0) == []      # split_test: 0 bits = off
     assert cases.walk_splitter_indices(4, "AAAAA", 4) == [1] and cases.count_walk_splitters(4, ["AAAAA", c], 0) == 0
+
+
+# ---- the route inputs of test_gpu_route.py --------------------------------------------------------
+@pytest.mark.parametrize("n", cases.ROUTE_SIZES)
+@pytest.mark.parametrize("k", [12, 13, 19, 22, 32, 51, 60])
+def test_route_inputs_vs_oracle(k, n):
+    """Exactly n distinct k-mers, the oracle's assembly is the builder's truth (in start-record
+    order, after the two lines changed places), starts in the first and in the last mask word, a
+    last word that is not full where n says so, a word without starts from one tile on."""
+    if k <= 13 and n > 2000:
+        n = 2000 - (n % 7)  # (test_gpu_route.py keeps to 2,000 records there)
+    text, contigs, seed = cases.route_text(k, n)
+    assert len(text) == n * (k + 4)
+    recs = ob.parse_text(k, text)
+    assert len(recs) == n and len(np.unique(recs[:, :(k + 3) // 4], axis=0)) == n
+    cases.RecordDict(k, recs)  # (asserts distinct keys as well)
+    rc, got, nc, nl, _, _ = ob.assemble(k, recs)
+    assert rc == 0 and nc == len(contigs) and nl == n - nc
+    assert got == cases.contigs_truth(contigs)
+    assert sorted(len(c) - k + 1 for c in contigs) == sorted(cases.route_lens(n, seed))
+    words = cases.start_mask_words(k, text)
+    assert len(words) == (n + 63) // 64 and words[0] and words[-1]
+    assert sum(bin(w).count("1") for w in words) == nc
+    assert words[0] & 1 and words[-1] >> ((n - 1) & 63) == 1  # the first and the last record are starts
+    if n >= 2047:
+        assert not all(words)
+        assert max(len(c) - k + 1 for c in contigs) >= 40 and min(len(c) - k + 1 for c in contigs) <= 4
+
+
+def test_route_lens_exact():
+    for n in cases.ROUTE_SIZES:
+        lens = cases.route_lens(n, n)
+        assert sum(lens) == n and min(lens) >= 1 and max(lens) <= 300
+        assert n < 2 or len(lens) >= 2
+
+
+def test_chunk_bounds():
+    assert cases.chunk_bounds(7169, 2) == [0, 3584, 7169]
+    assert cases.chunk_bounds(7169, 5, 2) == [0, 1792, 3584, 3584, 5376, 7169]
+    assert cases.chunk_bounds(1, 2, 0) == [0, 0, 1]
+    assert cases.chunk_bounds(257, 5) == [0, 48, 96, 144, 192, 257]
+    for n in cases.ROUTE_SIZES:
+        for calls, empty in ((2, None), (2, 0), (5, None), (5, 2)):
+            b = cases.chunk_bounds(n, calls, empty)
+            assert b[0] == 0 and b[-1] == n and len(b) == calls + 1
+            assert empty is None or b[empty] == b[empty + 1]
+
+
+def test_record_dict():
+    recs = ob.parse_text(19, cases.route_text(19, 257)[0])
+    d = cases.RecordDict(19, recs)
+    q = np.concatenate([recs[5:8, :5], np.zeros((1, 5), np.uint8) + 0xFF])
+    r, f = d.lookup(q)
+    assert f.tolist() == [1, 1, 1, 0] and np.array_equal(r[:3], recs[5:8]) and not r[3].any()
+    assert d.lookup(recs[:0, :5])[0].shape == (0, 7)
+    with pytest.raises(AssertionError):
+        cases.RecordDict(19, np.concatenate([recs, recs[:1]]))
+
+
+@pytest.mark.parametrize("k", [19, 51])
+def test_owned_subset_vs_oracle(k):
+    """The selection builder of the skewed route input with a stand-in owner function (the real one
+    needs a device table): a closed input whose oracle assembly is the kept contigs, nearly all of
+    its k-mers with the hot owner."""
+    _, contigs = cases.contigs_text(k, cases.short_lens(3000, k), seed=k)
+
+    def owner_of(kmer):  # consecutive k-mers mostly agree, as with a minimizer
+        return min(cases.split_hash(kmer[i:i + 8]) for i in range(k - 7)) % 8
+
+    text, kept, hot = cases.owned_subset_text(k, contigs, owner_of, 150, seed=k)
+    n = len(text) // (k + 4)
+    recs = ob.parse_text(k, text)
+    rc, got, nc, nl, _, _ = ob.assemble(k, recs)
+    assert rc == 0 and nc == len(kept) and got == cases.contigs_truth(kept)
+    assert len(np.unique(recs[:, :(k + 3) // 4], axis=0)) == n
+    own = [owner_of(text[i * (k + 4):i * (k + 4) + k].decode()) for i in range(n)]
+    assert own.count(hot) >= 0.9 * n and own.count(hot) < n

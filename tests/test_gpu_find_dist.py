@@ -1,7 +1,7 @@
 """GPU: the batched find across shards (kh_find_route_dev / kh_find_answer_dev / kh_find_gather_dev,
 DistributedKmerHashMap.find) with P logical ranks on one GPU (ThreadComm).
 
-Expected answers come from the input records themselves (key bytes -> record, RecordDict below),
+Expected answers come from the input records themselves (key bytes -> record, cases.RecordDict),
 never from the code under test: a present key gives its record and found = 1, an absent key a
 zeroed record and found = 0, byte for byte."""
 import ctypes
@@ -14,38 +14,12 @@ import numpy as np
 import pytest
 
 import cs267_hw3_amd as kh
+from cases import RecordDict
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 MANIFEST = json.load(open(os.path.join(GOLDEN, "manifest.json")))
-
-
-class RecordDict:
-    """key bytes -> record of a record array [n, R] (sorted keys + binary search)."""
-
-    def __init__(self, k, recs):
-        self.KP = (k + 3) // 4
-        self.R = self.KP + 2
-        keys = self._s(recs[:, :self.KP])
-        order = np.argsort(keys, kind="stable")
-        self.keys, self.recs = keys[order], np.ascontiguousarray(recs[order])
-        assert len(np.unique(self.keys)) == len(self.keys)
-
-    def _s(self, a):  # rows as fixed-width byte strings (compared like memcmp)
-        return np.ascontiguousarray(a, dtype=np.uint8).view(f"S{self.KP}").ravel()
-
-    def lookup(self, q):
-        """-> (records [m, R] (zeroed where absent), found uint8 [m])"""
-        q = np.ascontiguousarray(q, dtype=np.uint8).reshape(-1, self.KP)
-        out = np.zeros((len(q), self.R), np.uint8)
-        if not len(q):
-            return out, np.zeros(0, np.uint8)
-        v = self._s(q)
-        i = np.minimum(np.searchsorted(self.keys, v), len(self.keys) - 1)
-        hit = self.keys[i] == v
-        out[hit] = self.recs[i[hit]]
-        return out, hit.astype(np.uint8)
 
 
 def absent_keys(k, d, present, limit=None):
