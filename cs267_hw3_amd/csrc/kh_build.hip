@@ -248,6 +248,19 @@ __device__ __forceinline__ void parse_record_regs_t(uint64_t x0, uint64_t x1, in
     ext = ext_codes2(e);
 }
 
+// The same from the record's bytes already in big-endian order: be0..be3 = bytes 0-3, 4-7, 8-11 and
+// 12-15 of the record, each byte-reversed into a dword, e = the two extension bytes (k_win1_rec
+// gets all five with one v_perm_b32 each, straight from the dword-aligned words around the record).
+template <int PK>
+__device__ __forceinline__ void parse_record_be_t(uint32_t be0, uint32_t be1, uint32_t be2, uint32_t be3, uint32_t e,
+                                                  int pad, Key& k, uint32_t& ext) {
+    const unsigned __int128 be = ((unsigned __int128)(((uint64_t)be0 << 32) | be1) << 64) | (((uint64_t)be2 << 32) | be3);
+    const unsigned __int128 B = (be >> (8 * (16 - PK))) >> (2 * pad);
+    k.lo = (uint64_t)B & LO_MASK;
+    k.hi = (uint64_t)(B >> 62);
+    ext = ext_codes2(e);
+}
+
 // ---- build ------------------------------------------------------------------------------------
 // The region slice in LDS. W=2 slots are stored as two arrays (word 0 of slot i at w[i], word 1
 // at w[sm + i], sm = the block's slice capacity) rather than 16-B pairs: the random 8-B CAS, probe
@@ -1118,7 +1131,9 @@ __device__ __forceinline__ void load_words_win_tb(const uint64_t* __restrict__ b
 // LATE: g is published after next() issues the next tile's loads; only where those loads are
 // unconditional (the waitcnt for g then leaves them in flight: vmcnt(N)); behind conditional loads
 // the compiler waits for vmcnt(0), i.e. for the prefetch itself, so g is published before next().
-template <int W, int TB, int NB, int TILE, bool WRANK = false, bool LATE = true, class CtrF, class WinF, class NextF>
+// WBATCH: the write-out reads each LDS level for all of a thread's items at once (see there).
+template <int W, int TB, int NB, int TILE, bool WRANK = false, bool LATE = true, bool WBATCH = false, class CtrF,
+          class WinF, class NextF>
 __device__ __forceinline__ void sort_reserve_write(uint64_t* a, uint64_t* b, const uint32_t* bin, uint64_t* items,
                                                    uint16_t* sbin, uint32_t* hist, uint32_t* start, uint32_t* gpos,
                                                    uint32_t* wsum, CtrF counter, WinF window, uint32_t cap,
@@ -1160,28 +1175,61 @@ __device__ __forceinline__ void sort_reserve_write(uint64_t* a, uint64_t* b, con
             sbin[pos] = (uint16_t)bin[j];
         }
     }
+    // gpos holds g - start (mod 2^32): the write-out adds an item's sorted position x to it
+    // and reads one LDS word per item for its destination instead of two
     if (!LATE && threadIdx.x < NB) {
-        gpos[threadIdx.x] = g;
+        gpos[threadIdx.x] = g - st;
         if (hv && g + hv > cap) spill = 1;
     }
     __builtin_amdgcn_sched_barrier(0);
     next();  // the next tile's loads are in flight while this one is written
     if (LATE && threadIdx.x < NB) {
-        gpos[threadIdx.x] = g;
+        gpos[threadIdx.x] = g - st;
         if (hv && g + hv > cap) spill = 1;
     }
     lds_barrier();
+    if constexpr (WBATCH) {
+        // an item's destination is three dependent LDS reads (bin, its offset, the item): each
+        // level is read for all of the thread's items before the next one needs it, so the thread
+        // waits for three LDS round trips per tile instead of three per item. Only the records
+        // pass: the 8-item words passes have no registers left for it (k_win2 spilled to scratch).
+        uint32_t wq[IPT], ww[IPT];
+#pragma unroll
+        for (int i = 0; i < IPT; ++i) {
+            const uint32_t x = (uint32_t)i * TB + threadIdx.x;
+            wq[i] = x < total ? sbin[x] : 0u;
+        }
+#pragma unroll
+        for (int i = 0; i < IPT; ++i) {
+            const uint32_t x = (uint32_t)i * TB + threadIdx.x;
+            ww[i] = x < total ? gpos[wq[i]] + x : cap;  // cap: nothing to write
+        }
+#pragma unroll
+        for (int i = 0; i < IPT; ++i) {
+            const uint32_t x = (uint32_t)i * TB + threadIdx.x;
+            if (ww[i] < cap) {
+                const uint64_t v0 = items[x], v1 = (W == 2) ? items[TILE + x] : 0;
+                const uint64_t g = window(wq[i]) + ww[i];
+                if (W == 2) {
+                    *reinterpret_cast<ulonglong2*>(out + g * 2) = make_ulonglong2(v0, v1);
+                } else {
+                    out[g] = v0;
+                }
+            }
+        }
+    } else {
 #pragma unroll 4
-    for (uint32_t x = threadIdx.x; x < total; x += TB) {
-        const uint32_t q = sbin[x];
-        const uint32_t w = gpos[q] + (x - start[q]);
-        if (w < cap) {
-            const uint64_t v0 = items[x], v1 = (W == 2) ? items[TILE + x] : 0;
-            const uint64_t g = window(q) + w;
-            if (W == 2) {
-                *reinterpret_cast<ulonglong2*>(out + g * 2) = make_ulonglong2(v0, v1);
-            } else {
-                out[g] = v0;
+        for (uint32_t x = threadIdx.x; x < total; x += TB) {
+            const uint32_t q = sbin[x];
+            const uint32_t w = gpos[q] + x;
+            if (w < cap) {
+                const uint64_t v0 = items[x], v1 = (W == 2) ? items[TILE + x] : 0;
+                const uint64_t g = window(q) + w;
+                if (W == 2) {
+                    *reinterpret_cast<ulonglong2*>(out + g * 2) = make_ulonglong2(v0, v1);
+                } else {
+                    out[g] = v0;
+                }
             }
         }
     }
@@ -1193,7 +1241,6 @@ __device__ __forceinline__ void sort_reserve_write(uint64_t* a, uint64_t* b, con
         __shared__ unsigned long long sbase;
         uint32_t sp = 0;
         if (threadIdx.x < NB) {
-            const uint32_t g = gpos[threadIdx.x];
             const uint32_t keep = g >= cap ? 0u : min(hv, cap - g);
             keepv[threadIdx.x] = keep;
             sp = hv - keep;
@@ -1337,6 +1384,7 @@ __global__ __launch_bounds__(TB) void k_win1_rec(KParams p_in, const uint8_t* __
         __syncthreads();
     }
     constexpr int IPT = TILE / TB;
+    static_assert(TILE % TB == 0 && TB % 64 == 0, "a wave's 64 records start on a 16-B boundary");
     const bool hot_on = !ROUTE && p.hot && ctr[CT_HOT];
     extern __shared__ __attribute__((aligned(16))) uint64_t smem[];
     uint64_t* items = smem;
@@ -1354,6 +1402,17 @@ __global__ __launch_bounds__(TB) void k_win1_rec(KParams p_in, const uint8_t* __
     const uint32_t R = PK ? (uint32_t)(PK + 2) : (uint32_t)p.R;  // PK = 0: any record of <= 15 bytes
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t nbytes = n * (uint64_t)R;
+    // LDS staging of the raw blocks, 1 KiB per wave and sub-tile: the sort's item area, free while
+    // a tile is parsed (the sort's last barrier ends the previous tile's write-out, its first one
+    // precedes the scatter); the route has no item area and reuses one static slot per wave
+    static_assert((TB / 64) * IPT * 1024 <= TILE * 16, "staging slots fit the item area");
+    __shared__ __attribute__((aligned(16))) uint8_t rstage[ROUTE ? (TB / 64) * 1024 : 16];
+    uint8_t* stage = ROUTE ? rstage + (threadIdx.x >> 6) * 1024u
+                           : reinterpret_cast<uint8_t*>(smem) + (threadIdx.x >> 6) * (uint32_t)(IPT * 1024);
+    const uint32_t roff = lane * R;                        // the lane's record within the wave's run (<= 945)
+    const uint32_t rsh = roff & 3u;                        // ... within its first dword
+    const uint32_t sel_be = 0x00010203u + rsh * 0x01010101u;            // bytes rsh + 3 .. rsh of a dword pair
+    const uint32_t sel_ext = 0x0C0C0000u | ((rsh + 2u) << 8) | (rsh + 1u);  // bytes rsh + 1, rsh + 2, zero above
     uint64_t a[IPT], b[IPT];  // raw 16-B blocks until parsed, then the words
     // ROUTE: loads only where a block is needed. Otherwise every lane loads
     // (its address clamped into the records): blocks 62 and 63 and those of a wave past the batch
@@ -1395,24 +1454,30 @@ __global__ __launch_bounds__(TB) void k_win1_rec(KParams p_in, const uint8_t* __
             Key k{0, 0};
             uint32_t ext = 0;
             {
-                const uint64_t r0 = s0 + (threadIdx.x & ~63u);
-                const uint32_t off = (uint32_t)((r0 * R) & 15u) + lane * R;  // from the first block
-                const int blk = (int)(off >> 4);
-                const uint32_t o = off & 15u;
-                const uint64_t p0 = __shfl(a[j], blk, 64), p1 = __shfl(b[j], blk, 64);
-                const uint64_t q0 = __shfl(a[j], blk + 1, 64), q1 = __shfl(b[j], blk + 1, 64);
-                uint64_t w0 = p0, w1 = p1, w2 = q0;
-                if (o >= 8u) {
-                    w0 = p1;
-                    w1 = q0;
-                    w2 = q1;
-                }
-                const uint32_t sh = (o & 7u) * 8u;
-                if (valid) {
-                    if constexpr (PK != 0)
-                        parse_record_regs_t<PK>(funnel64(w0, w1, sh), funnel64(w1, w2, sh), p.pad, k, ext);
-                    else
-                        parse_record_regs(funnel64(w0, w1, sh), funnel64(w1, w2, sh), p, k, ext);
+                // the wave's blocks go through its LDS staging slot: one 16-B write per lane, then
+                // the five dword-aligned words around the lane's record (the run starts on a 16-B
+                // boundary: the wave's first record index is a multiple of 64). DS operations of
+                // one wave execute in order, so the slot needs no barrier.
+                uint8_t* sj = stage + (ROUTE ? 0 : j * 1024);
+                *reinterpret_cast<ulonglong2*>(sj + lane * 16u) = make_ulonglong2(a[j], b[j]);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                const uint32_t* q = reinterpret_cast<const uint32_t*>(sj + (roff & ~3u));
+                const uint32_t d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3], d4 = q[4];
+                // parsed for every lane (registers only): what a lane past the batch parses is unused
+                if constexpr (PK != 0) {
+                    // byte alignment and the parse's byte reversal in one v_perm_b32 per dword
+                    static_assert(PK % 4 == 1 && PK <= 13, "extension bytes at bytes 1, 2 of dword (PK - 1) / 4");
+                    const uint32_t dq[5] = {d0, d1, d2, d3, d4};
+                    constexpr int EQ = (PK - 1) / 4;
+                    parse_record_be_t<PK>(__builtin_amdgcn_perm(d1, d0, sel_be), __builtin_amdgcn_perm(d2, d1, sel_be),
+                                          __builtin_amdgcn_perm(d3, d2, sel_be), __builtin_amdgcn_perm(d4, d3, sel_be),
+                                          __builtin_amdgcn_perm(dq[EQ + 1], dq[EQ], sel_ext), p.pad, k, ext);
+                } else {
+                    const uint32_t x0 = __builtin_amdgcn_alignbyte(d1, d0, rsh), x1 = __builtin_amdgcn_alignbyte(d2, d1, rsh),
+                                   x2 = __builtin_amdgcn_alignbyte(d3, d2, rsh), x3 = __builtin_amdgcn_alignbyte(d4, d3, rsh);
+                    parse_record_regs(((uint64_t)x1 << 32) | x0, ((uint64_t)x3 << 32) | x2, p, k, ext);
                 }
             }
             const uint32_t mn = mini_scan(k, p);
@@ -1434,7 +1499,7 @@ __global__ __launch_bounds__(TB) void k_win1_rec(KParams p_in, const uint8_t* __
                 if (spl && valid && ext_bwd(ext) != EXT_F && is_splitter(k, p))
                     atomicAdd(&rspl[bin[j]], 1u);
             } else
-                bin[j] = part_region(mini_window(k, mn, p), k, p, hot_on, (int)(mn & 63u)) >> (p.rbits - B1);
+                bin[j] = part_region(win_bits_sel(k, mn & 63u, p), k, p, hot_on, (int)(mn & 63u)) >> (p.rbits - B1);
         }
         const uint64_t nt = t + gridDim.x, nbase = nt * TILE;
         if constexpr (ROUTE) {
@@ -1465,7 +1530,7 @@ __global__ __launch_bounds__(TB) void k_win1_rec(KParams p_in, const uint8_t* __
             load(nbase, nt < ntiles ? min(nbase + TILE, n) : nbase);
             lds_barrier();  // every lane has read rg before the next tile's counts
         } else {
-            sort_reserve_write<W, TB, NB, TILE, false, UNCOND>(
+            sort_reserve_write<W, TB, NB, TILE, false, UNCOND, true>(
                 a, b, bin, items, sbin, hist, start, gpos, wsum, [&](uint32_t q) { return &wcnt[q * S1 + sub]; },
                 [&](uint32_t q) { return (uint64_t)(q * S1 + sub) * CAP1; }, CAP1, buf1, ovf, ovf_cap, ctr, stats,
                 [&]() { load(nbase, nt < ntiles ? min(nbase + TILE, n) : nbase); });

@@ -319,6 +319,19 @@ __device__ __forceinline__ uint32_t mini_scan_t(Key k) {
 }
 #endif
 
+// win_bits on the scan's 32-bit words: window j starts in word 2j >> 5, so its bits are one
+// funnel shift (v_alignbit_b32) of two selected words instead of win_bits' three variable 64-bit
+// shifts behind a divergent branch. Same value as win_bits(k, j, p) for 0 <= j <= K - M.
+KH_HD uint32_t win_bits_sel(Key k, uint32_t j, const KParams& p) {
+    const uint32_t v0 = (uint32_t)k.lo, v1 = (uint32_t)(k.lo >> 32) | (uint32_t)(k.hi << 30),
+                   v2 = (uint32_t)(k.hi >> 2), v3 = (uint32_t)(k.hi >> 34);
+    const uint32_t b = 2u * j, i = b >> 5;
+    const bool far = 2 * (p.K - p.M) >= 96;  // some window starts in word 3 (no compile-time shape does)
+    const uint32_t lo = i == 0 ? v0 : (i == 1 ? v1 : ((far && i == 3) ? v3 : v2));
+    const uint32_t hi = i == 0 ? v1 : (i == 1 ? v2 : ((far && i == 3) ? 0u : v3));
+    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (b & 31u)) & (uint32_t)((1ull << (2 * p.M)) - 1);
+}
+
 KH_HD uint32_t mini_scan(Key k, const KParams& p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     if (p.K == 51 && p.M == 16) return mini_scan_t<51, 16>(k);  // uniform branches
