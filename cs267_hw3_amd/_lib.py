@@ -54,6 +54,8 @@ def slot_words(cap):
     return 2 + cap * MSG_WORDS
 
 SEG_REC_WORDS = 3  # KH_SEG_REC_WORDS
+TEXT_NONE = 0xFF  # KH_TEXT_NONE: find over text, no window at the position
+TEXT_TILE = 2048  # KH_TEXT_TILE: text positions per block of the text kernels
 
 _SIGS = {
     "kh_abi_version": (ctypes.c_int, []),
@@ -98,6 +100,9 @@ _SIGS = {
     "kh_find_route_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_vp]),
     "kh_find_answer_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp]),
     "kh_find_gather_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_vp, c_vp, c_vp]),
+    "kh_find_text_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_vp]),
+    "kh_find_text": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_vp]),
+    "kh_text_keys_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_vp, c_vp]),
     "kh_mwalk_begin": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, c_u64, c_u64, c_u64, c_u64,
                                       ctypes.POINTER(c_u64)]),
     "kh_mwalk_round_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_u64, c_vp]),

@@ -121,6 +121,7 @@ struct kh_table {
     DevBuf contig_len, contig_off, chunk_data, chunk_owner, chunk_seq, text, line_first;
     DevBuf route_hist, route_off, route_scratch, route_own;                       // sharded path
     DevBuf find_own, find_ext;                // batched find: owners of routed keys / answers in key order
+    DevBuf text_cnt, text_off, text_scratch;  // kh_text_keys_dev: windows per tile, their offsets, the scan's sums
     DevBuf pb_buf1, pb_buf2, pb_cnt, pb_ovf;  // partitioned build
     DevBuf headrec;                           // chain head records (region build -> walker)
     DevBuf hot;                               // remapped-region bitmap (KParams::hot), 2 levels of HOT_WORDS
@@ -447,7 +448,7 @@ int kh_destroy(kh_table* t) {
                       &t->mw_cnt, &t->mw_list, &t->mw_carry[0], &t->mw_carry[1], &t->mw_carry_dst[0],
                       &t->mw_carry_dst[1], &t->ms_res[0], &t->ms_res[1], &t->ms_res[2], &t->ms_res[3], &t->ms_res[4],
                       &t->ms_res[5], &t->ms_pend, &t->route_spl, &t->find_own, &t->find_ext,
-                      &t->pb_buf1, &t->pb_buf2, &t->pb_cnt, &t->pb_ovf, &t->headrec, &t->hot, &t->rbounds};
+                      &t->text_cnt, &t->text_off, &t->text_scratch, &t->pb_buf1, &t->pb_buf2, &t->pb_cnt, &t->pb_ovf, &t->headrec, &t->hot, &t->rbounds};
     if (t->side) (void)hipStreamSynchronize(t->side);  // k_rec_succ may still read the table
     for (auto* b : bufs) b->release();
     hipEvent_t evs[] = {t->ev_ins0, t->ev_ins1, t->ev_ins2, t->ev_walk0, t->ev_walk1, t->ev_mat1, t->ev_b0,
@@ -1236,6 +1237,67 @@ int kh_find_gather_dev(kh_table* t, const void* dev_keys, uint64_t n, const void
     KH_HIP(kh::launch_find_gather(t->kp, (const uint8_t*)dev_keys, n, (const uint32_t*)dev_index,
                                   (const uint8_t*)dev_ext_grouped, t->find_ext.as<uint16_t>(), (uint8_t*)dev_recs_out,
                                   (uint8_t*)dev_found_out, t->stream));
+    return KH_OK;
+}
+
+// ---- find over text (kh_text.hip) ---------------------------------------------------------------
+static_assert(KH_TEXT_TILE == kh::TEXT_TILE, "text tile of the header comment");
+
+int kh_find_text_dev(kh_table* t, const void* dev_text, uint64_t len, void* dev_ext_out, void* dev_counts_out) {
+    if (!t) return fail(KH_ERR_ARG, "null table");
+    if (t->staging) return fail(KH_ERR_STATE, "a staged insert is open (kh_insert_words_finish first)");
+    if (!dev_ext_out && !dev_counts_out) return fail(KH_ERR_ARG, "no output buffer");
+    if (len == 0) return KH_OK;
+    if (!dev_text) return fail(KH_ERR_ARG, "null text");
+    if ((uintptr_t)dev_counts_out & 7u) return fail(KH_ERR_ARG, "counts must be 8-byte aligned");
+    if (int rc = set_device(t)) return rc;
+    if (int rc = clean_slots(t)) return rc;
+    KH_HIP(kh::launch_find_text(t->kp, (const uint8_t*)dev_text, len, view(t), (uint8_t*)dev_ext_out,
+                                (unsigned long long*)dev_counts_out, t->stream));
+    return KH_OK;
+}
+
+int kh_find_text(kh_table* t, const char* host_text, uint64_t len, uint8_t* host_ext_out, uint64_t* counts2) {
+    if (!t) return fail(KH_ERR_ARG, "null table");
+    if (t->staging) return fail(KH_ERR_STATE, "a staged insert is open (kh_insert_words_finish first)");
+    if (!host_ext_out && !counts2) return fail(KH_ERR_ARG, "no output buffer");
+    if (len == 0) return KH_OK;
+    if (!host_text) return fail(KH_ERR_ARG, "null text");
+    if (int rc = set_device(t)) return rc;
+    int rc;
+    if ((rc = t->stage.ensure(len))) return rc;
+    if (host_ext_out && (rc = t->stage2.ensure(2 * len))) return rc;
+    if ((rc = t->stage3.ensure(16))) return rc;
+    KH_HIP(hipMemcpyAsync(t->stage.p, host_text, len, hipMemcpyHostToDevice, t->stream));
+    if ((rc = kh_find_text_dev(t, t->stage.p, len, host_ext_out ? t->stage2.p : nullptr, t->stage3.p))) return rc;
+    if (host_ext_out) KH_HIP(hipMemcpyAsync(host_ext_out, t->stage2.p, 2 * len, hipMemcpyDeviceToHost, t->stream));
+    uint64_t c[2] = {0, 0};
+    KH_HIP(hipMemcpyAsync(c, t->stage3.p, 16, hipMemcpyDeviceToHost, t->stream));
+    KH_SYNC(t);
+    if (counts2) {
+        counts2[0] = c[0];
+        counts2[1] = c[1];
+    }
+    return KH_OK;
+}
+
+int kh_text_keys_dev(kh_table* t, const void* dev_text, uint64_t len, void* dev_keys_out, void* dev_pos_out,
+                     void* dev_count_out) {
+    if (!t) return fail(KH_ERR_ARG, "null table");
+    if (len >> 32) return fail(KH_ERR_ARG, "%llu bytes of text in one call (positions are 32-bit)", (unsigned long long)len);
+    if (!dev_count_out || (len && !dev_text)) return fail(KH_ERR_ARG, "null buffer");
+    if (!dev_keys_out != !dev_pos_out) return fail(KH_ERR_ARG, "keys and positions go together (both null: count only)");
+    if ((uintptr_t)dev_pos_out & 3u) return fail(KH_ERR_ARG, "positions must be 4-byte aligned");
+    if ((uintptr_t)dev_count_out & 7u) return fail(KH_ERR_ARG, "the count must be 8-byte aligned");
+    if (int rc = set_device(t)) return rc;
+    const uint64_t nt = kh::text_tiles(len);
+    int rc;
+    if ((rc = t->text_cnt.ensure((nt + 1) * 8)) || (rc = t->text_off.ensure((nt + 1) * 8)) ||
+        (rc = t->text_scratch.ensure(kh::scan_scratch_words(nt) * 8 + 64)))
+        return rc;
+    KH_HIP(kh::launch_text_keys(t->kp, (const uint8_t*)dev_text, len, t->text_cnt.as<uint64_t>(),
+                                t->text_off.as<uint64_t>(), t->text_scratch.as<uint64_t>(), (uint8_t*)dev_keys_out,
+                                (uint32_t*)dev_pos_out, (unsigned long long*)dev_count_out, t->stream));
     return KH_OK;
 }
 

@@ -373,6 +373,21 @@ hipError_t launch_find_gather(const KParams& p, const uint8_t* keys, uint64_t n,
                               const uint8_t* ext_grouped, uint16_t* ext_orig, uint8_t* recs_out, uint8_t* found_out,
                               hipStream_t s);
 
+// Find over text (kh_text.hip). A block works on TEXT_TILE positions of the text (+ a K-1 byte halo).
+static constexpr int TEXT_TILE = 2048;
+inline uint64_t text_tiles(uint64_t len) { return (len + TEXT_TILE - 1) / TEXT_TILE; }
+// len bytes of text (any alignment) -> ext_out (null: none): 2 bytes per position, {backward, forward}
+// chars of the k-mer at that position, {0, 0} = absent, {0xFF, 0xFF} = no window there; counts (null:
+// none, else zeroed first): {windows, found}.
+hipError_t launch_find_text(const KParams& p, const uint8_t* text, uint64_t len, TableView t, uint8_t* ext_out,
+                            unsigned long long* counts, hipStream_t s);
+// The text's windows as PACKED-byte keys and their uint32 positions, ascending (both null: count
+// only); *count_out = their number. len < 2^32; tile_cnt / tile_off: text_tiles(len) words each,
+// scratch: scan_scratch_words(text_tiles(len)).
+hipError_t launch_text_keys(const KParams& p, const uint8_t* text, uint64_t len, uint64_t* tile_cnt,
+                            uint64_t* tile_off, uint64_t* scratch, uint8_t* keys_out, uint32_t* pos_out,
+                            unsigned long long* count_out, hipStream_t s);
+
 }  // namespace kh
 
 // ---- partitioned (atomic-free) bulk build ------------------------------------------------------

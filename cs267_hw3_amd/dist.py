@@ -442,6 +442,30 @@ class GpuShard:
                                         self._p(found)))
         return recs[:n], found[:n]
 
+    # find over text (kh_text.hip): text is a 1-D uint8 device tensor
+    def find_text(self, text):
+        """Every k-mer of the text looked up in this shard -> (uint8 [len, 2]: {backward, forward}
+        chars, {0, 0} = absent, {0xFF, 0xFF} = no window at the position; int64 [2]: windows, found)
+        (kh_find_text_dev)."""
+        n = text.numel()
+        ext = torch.empty((max(n, 1), 2), dtype=torch.uint8, device=self.dev)
+        counts = torch.zeros(2, dtype=torch.int64, device=self.dev)  # the call writes nothing for an empty text
+        check(self.L.kh_find_text_dev(self.h, self._p(text), n, self._p(ext), self._p(counts)))
+        return ext[:n], counts
+
+    def text_keys(self, text):
+        """The text's windows -> (pkmer_t keys uint8 [max(len-k+1, 0), PACKED], their positions as
+        int32 bit patterns of uint32, int64 [1]: how many of both are valid), in ascending position
+        (kh_text_keys_dev)."""
+        n = text.numel()
+        kp = (self.k + 3) // 4
+        m = max(n - self.k + 1, 0)
+        keys = torch.empty((max(m, 1), kp), dtype=torch.uint8, device=self.dev)
+        pos = self.zeros(m, torch.int32)
+        count = self.zeros(1, torch.int64)
+        check(self.L.kh_text_keys_dev(self.h, self._p(text), n, self._p(keys), self._p(pos), self._p(count)))
+        return keys[:m], pos[:m], count
+
     # migrating-walker rounds (fixed-size exchange slots: no device read per round)
     MSG_WORDS = _lib.MSG_WORDS
     TEXT_REC_WORDS = _lib.TEXT_REC_WORDS
@@ -895,6 +919,45 @@ class DistributedKmerHashMap:
         if host:
             return recs.cpu().numpy(), found.cpu().numpy().astype(bool)
         return recs, found
+
+    def find_text(self, text):
+        """find() for every k-mer of a text (reads, contig lines, FASTA; KmerHashTable.find_text's
+        semantics), whichever rank holds it. Collective: every rank calls it; its own text may be
+        empty and differ between ranks. text: a 1-D uint8 device tensor -> (ext uint8 [len, 2],
+        counts int64 [2] = windows, found) device tensors; or host bytes / a numpy uint8 array ->
+        (ext numpy [len, 2], windows, found). Byte-identical to KmerHashTable.find_text on one
+        table holding every k-mer.
+
+        The shard cuts the text into keys and positions (text_keys), find() answers the keys across
+        the ranks, and the answers are placed by position. One blocking host read more than find()
+        (the window count). One rank without a forced self-exchange: the fused kernel."""
+        sh, P = self.shard, self.P
+        kp = (sh.k + 3) // 4
+        host = not torch.is_tensor(text)
+        if host:
+            import numpy as np
+            text = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else \
+                np.ascontiguousarray(text, dtype=np.uint8).ravel()
+            text = torch.from_numpy(text.copy())
+            if getattr(sh, "dev", None) is not None:
+                text = text.to(sh.dev)
+        text = text.contiguous().view(-1)
+        n = text.numel()
+        if P == 1 and not self.SELF_EXCHANGE:
+            ext, counts = sh.find_text(text)
+        else:
+            keys, pos, count = sh.text_keys(text)
+            m = int(self._host(count)[0])
+            recs, found = self.find(keys[:m])
+            ext = torch.full((n, 2), _lib.TEXT_NONE, dtype=torch.uint8, device=text.device)
+            ext[pos[:m].long() & 0xFFFFFFFF] = recs[:, kp:kp + 2]  # an absent key's record is zeroed
+            counts = torch.zeros(2, dtype=torch.int64, device=text.device)
+            counts[0] = m
+            counts[1] = found.sum(dtype=torch.int64)
+        if host:
+            c = counts.cpu().tolist()
+            return ext.cpu().numpy(), int(c[0]), int(c[1])
+        return ext, counts
 
     def assemble(self, total_kmers):
         """Walk this rank's start k-mers (collective); returns the number of rounds. Walks that

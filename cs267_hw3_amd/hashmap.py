@@ -181,6 +181,26 @@ class KmerHashTable:
             check(self._L.kh_find(self._h, _ptr(keys), n, _ptr(out), _ptr(found)))
         return out, found.astype(bool)
 
+    def find_text(self, text):
+        """Every k-mer of a text (bytes or a numpy uint8 array: reads, contig lines, FASTA) looked up:
+        -> (ext uint8 [len, 2], windows, found). ext[i] = the {backward, forward} chars of the k-mer
+        at bytes i .. i+k-1, {0, 0} when the table does not hold it, {0xFF, 0xFF} (KH_TEXT_NONE) when
+        those bytes are not all in the text and one of A C G T."""
+        buf = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else \
+            np.ascontiguousarray(text, dtype=np.uint8).ravel()
+        ext = np.empty((buf.size, 2), dtype=np.uint8)
+        counts = np.zeros(2, dtype=np.uint64)
+        check(self._L.kh_find_text(self._h, _ptr(buf) if buf.size else None, buf.size, _ptr(ext), _ptr(counts)))
+        return ext, int(counts[0]), int(counts[1])
+
+    def find_text_dev(self, text_ptr, nbytes, ext_ptr, counts_ptr):
+        """Asynchronous device form (kh_find_text_dev): nbytes of text at text_ptr -> 2 * nbytes answer
+        bytes at ext_ptr (0 / None: counts only) and 2 uint64 {windows, found} at counts_ptr (0 / None:
+        answers only). nbytes = 0 writes nothing."""
+        check(self._L.kh_find_text_dev(self._h, ctypes.c_void_p(text_ptr) if text_ptr else None, int(nbytes),
+                                       ctypes.c_void_p(ext_ptr) if ext_ptr else None,
+                                       ctypes.c_void_p(counts_ptr) if counts_ptr else None))
+
     # -- assemble -------------------------------------------------------------------------
     def set_starts(self, recs):
         recs, n = self._recs(recs)

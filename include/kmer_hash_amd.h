@@ -112,6 +112,38 @@ int kh_find(kh_table* t, const uint8_t* host_keys, uint64_t n, uint8_t* host_rec
 int kh_find_dev(kh_table* t, const void* dev_keys, uint64_t n, void* dev_recs_out,
                 void* dev_found);
 
+/* ---- find over text: every k-mer of a batch of sequences ---------------------------------------
+ * Batches DistributedHashMap::find / HashMap::find (hash_map.hpp:83-107) over read_kmers.hpp-style
+ * text: the caller hands over the bytes of reads, contigs (test_<rank>.dat) or FASTA lines instead
+ * of cutting, 2-bit-packing and uploading PACKED bytes per k-mer.
+ *   input   len bytes of text, any alignment.
+ *   window  position i has a window iff bytes i .. i+K-1 all lie in the text and are each one of
+ *           A C G T (upper case). Any other byte ('\n', '\r', space, N, F, lower case, 0, 0xFF, ...)
+ *           ends the windows that would cover it, so line structure needs no parsing; a header
+ *           line yields whatever windows its letters form.
+ *   answer  2 bytes per position: the k-mer is in the table: the {backward, forward} extension
+ *           chars of its record, as kh_find_answer_dev gives them; window present, k-mer absent:
+ *           {0, 0}; no window at i: {KH_TEXT_NONE, KH_TEXT_NONE}.
+ *   counts  2 uint64 {windows, found}.
+ *   len == 0: KH_OK, nothing written. len < K: every position NONE, counts {0, 0}.
+ *   An empty or cleared table answers absent for every window; a staged insert left open:
+ *   KH_ERR_STATE. Legal before and after assemble; changes neither the table, the start list nor
+ *   a walk. The kernel works on tiles of KH_TEXT_TILE positions (+ a K-1 byte halo) per block. */
+#define KH_TEXT_NONE 0xFF
+#define KH_TEXT_TILE 2048
+/* async on the table's stream; dev_ext_out: 2*len bytes or NULL (counts only); dev_counts_out:
+ * 2 uint64 (8-byte aligned) or NULL; both NULL, a null text with len > 0: KH_ERR_ARG. Text and
+ * answers may have any alignment. */
+int kh_find_text_dev(kh_table* t, const void* dev_text, uint64_t len, void* dev_ext_out, void* dev_counts_out);
+/* synchronous host form (staged upload / download like kh_find); either output may be NULL */
+int kh_find_text(kh_table* t, const char* host_text, uint64_t len, uint8_t* host_ext_out, uint64_t* counts2);
+/* the windows of the text as pkmer_t keys, in ascending position: keys_out holds up to
+ * max(len-K+1, 0) keys of PACKED bytes (any alignment), pos_out the uint32 position of each,
+ * count_out 1 uint64 on the device (always written). keys_out and pos_out both NULL: the count
+ * only. len >= 2^32: KH_ERR_ARG. Async; needs no table contents (works on an empty table). */
+int kh_text_keys_dev(kh_table* t, const void* dev_text, uint64_t len, void* dev_keys_out, void* dev_pos_out,
+                     void* dev_count_out);
+
 /* ---- assemble --------------------------------------------------------------------------------
  * Walks every start k-mer (collected by the inserts, or replaced by kh_set_starts) until its
  * forward extension is 'F', producing the contig text in start-node order on the device. */
