@@ -60,7 +60,7 @@ hipError_t launch_fill(const FillSet& f, hipStream_t s);
 
 // Chunk of appended bases: 8 words x 32 bases (2 bits each) = 256 bases.
 static constexpr int CHUNK_WORDS = 8;
-static constexpr uint32_t WMIN_ERR = 0xFFFFFFFFu;  // origin_lines (kh_capi.cpp): no memory
+static constexpr uint32_t WMIN_ERR = 0xFFFFFFFFu;  // origin_lines (kh_capi_dist.cpp): no memory
 static constexpr int CHUNK_BASES = 256;
 
 struct TableView {

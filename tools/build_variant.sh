@@ -16,7 +16,7 @@ else
   cd $R/cs267_hw3_amd/csrc
 fi
 PIDS=()
-for f in kh_kernels.hip kh_build.hip kh_mwalk.hip kh_mseg.hip kh_gen.hip kh_capi.cpp kh_host.cpp; do
+for f in *.hip kh_capi*.cpp kh_host.cpp; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function "$@" -c $f -o $D/obj/$f.o &
   PIDS+=($!)
 done
