@@ -56,6 +56,7 @@ def slot_words(cap):
 SEG_REC_WORDS = 3  # KH_SEG_REC_WORDS
 TEXT_NONE = 0xFF  # KH_TEXT_NONE: find over text, no window at the position
 TEXT_TILE = 2048  # KH_TEXT_TILE: text positions per block of the text kernels
+LOC_NONE = 0xFFFFFFFFFFFFFFFF  # KH_LOC_NONE: the position index has no position
 
 _SIGS = {
     "kh_abi_version": (ctypes.c_int, []),
@@ -103,6 +104,15 @@ _SIGS = {
     "kh_find_text_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_vp]),
     "kh_find_text": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_vp]),
     "kh_text_keys_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_vp, c_vp]),
+    "kh_locate_reset": (ctypes.c_int, [c_vp]),
+    "kh_locate_drop": (ctypes.c_int, [c_vp]),
+    "kh_locate_build": (ctypes.c_int, [c_vp]),
+    "kh_locate_set_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_vp]),
+    "kh_locate_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp]),
+    "kh_locate": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp]),
+    "kh_locate_text_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_vp]),
+    "kh_locate_text": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_vp]),
+    "kh_locate_lines_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_vp]),
     "kh_mwalk_begin": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, c_u64, c_u64, c_u64, c_u64,
                                       ctypes.POINTER(c_u64)]),
     "kh_mwalk_round_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_u64, c_vp]),

@@ -1,7 +1,8 @@
 // kh_capi.cpp — C ABI implementation (include/kmer_hash_amd.h), core part: errors, device buffers,
 // table lifetime, HIP streams/events, lookups on one table, stats and the device memory helpers.
 // The insert pipeline is in kh_capi_insert.cpp, the single-GPU walk in kh_capi_walk.cpp, the sharded
-// path (routes, batched find, text, migrating walk) in kh_capi_dist.cpp; kh_table.hpp is what they share.
+// path (routes, batched find, text, migrating walk) in kh_capi_dist.cpp, the position index in
+// kh_capi_locate.cpp; kh_table.hpp is what they share.
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -279,7 +280,7 @@ int kh_destroy(kh_table* t) {
                       &t->mw_cnt, &t->mw_list, &t->mw_carry[0], &t->mw_carry[1], &t->mw_carry_dst[0],
                       &t->mw_carry_dst[1], &t->ms_res[0], &t->ms_res[1], &t->ms_res[2], &t->ms_res[3], &t->ms_res[4],
                       &t->ms_res[5], &t->ms_pend, &t->route_spl, &t->find_own, &t->find_ext,
-                      &t->text_cnt, &t->text_off, &t->text_scratch, &t->pb_buf1, &t->pb_buf2, &t->pb_cnt, &t->pb_ovf, &t->headrec, &t->hot, &t->rbounds};
+                      &t->text_cnt, &t->text_off, &t->text_scratch, &t->pb_buf1, &t->pb_buf2, &t->pb_cnt, &t->pb_ovf, &t->headrec, &t->hot, &t->rbounds, &t->loc};
     if (t->side) (void)hipStreamSynchronize(t->side);  // k_rec_succ may still read the table
     for (auto* b : bufs) b->release();
     hipEvent_t evs[] = {t->ev_ins0, t->ev_ins1, t->ev_ins2, t->ev_walk0, t->ev_walk1, t->ev_mat1, t->ev_b0,
@@ -323,6 +324,7 @@ int kh_reserve(kh_table* t, uint64_t n_kmers) {
     t->slots = ns;
     ns.p = nullptr;
     t->slots_stale = true;
+    t->loc_valid = false;  // one position per slot of the old array
     kh::launch_bounds(t->kp, t->cap, nullptr, 0, t->rbounds.as<uint64_t>(), t->stream);
     KH_HIP(hipGetLastError());
     return KH_OK;
@@ -341,7 +343,7 @@ int kh_clear(kh_table* t) {
     f.add(t->route_spl.p, kh::MAX_RANKS * 8, 0);
     KH_HIP(kh::launch_fill(f, t->stream));
     t->n_inserted = 0;
-    t->assembled = false;
+    t->assembled = t->loc_valid = false;
     t->split_ok = true;
     t->starts_explicit = false;
     t->staging = false;

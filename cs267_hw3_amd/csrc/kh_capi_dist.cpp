@@ -53,7 +53,7 @@ int route_starts_close(kh_table* t, const void* dev_recs, uint64_t n, uint64_t* 
     if (n)
         if (int rc = collect_marks(t, (const uint8_t*)dev_recs, n, start_mask, nullptr, t->stream)) return rc;
     t->collected_n += n;
-    t->assembled = false;
+    t->assembled = t->loc_valid = false;
     return KH_OK;
 }
 
@@ -330,6 +330,7 @@ int mwalk_end_close(kh_table* t) {
     t->walk_timed = true;
     t->last_contigs = t->ms_ns;
     t->assembled = true;
+    t->loc_valid = false;  // a new text: positions in the last one mean nothing
     t->mw_live = false;
     return KH_OK;
 }
@@ -431,7 +432,7 @@ int kh_mwalk_begin(kh_table* t, int nranks, int rank, uint64_t total_kmers, uint
     }
     t->mw_live = true;
     t->mw_stepped = false;
-    t->assembled = false;
+    t->assembled = t->loc_valid = false;
     if (n_walkers) *n_walkers = nseg;
     return KH_OK;
 }
@@ -550,7 +551,7 @@ int kh_mwalk_abandon(kh_table* t) {
     if (int rc = join_succ(t)) return rc;
     KH_HIP(hipMemsetAsync(t->stats.as<unsigned long long>() + kh::ST_CHUNK_OVF, 0, 8, t->stream));
     t->mw_live = false;
-    t->assembled = false;
+    t->assembled = t->loc_valid = false;
     return KH_OK;
 }
 
@@ -563,7 +564,7 @@ int kh_mwalk_redo(kh_table* t, uint64_t store_records) {
     t->mw_seg_off = true;
     t->mw_store_min = store_records;
     t->mw_live = false;
-    t->assembled = false;
+    t->assembled = t->loc_valid = false;
     return KH_OK;
 }
 

@@ -172,7 +172,7 @@ int insert_close(kh_table* t, uint64_t n, bool part, bool side = false) {
     KH_HIP(hipEventRecord(t->ev_ins2, t->stream));
     t->ins_timed = true;
     t->n_inserted += n;
-    t->assembled = false;
+    t->assembled = t->loc_valid = false;
     return KH_OK;
 }
 
@@ -354,6 +354,7 @@ int kh_insert_words_stage_dev(kh_table* t, const void* words, uint64_t m, uint64
         t->stage_part = p.part;
         t->stage_fresh = p.fresh;
         t->staging = true;
+        t->loc_valid = false;
         t->last_insert_part = t->stage_part;  // already here: kh_get_stats between stage and finish
         if (t->stage_part)
             KH_HIP(kh::launch_part_stage(t->kp, nullptr, 0, total_hint, true, p.pb, t->ctr.as<unsigned long long>(),
@@ -414,7 +415,7 @@ int kh_collect_starts_dev(kh_table* t, const void* dev_recs, uint64_t n) {
     if ((rc = mark_buffers(t, n, have, 0, &start_mask, nullptr))) return rc;
     KH_HIP(kh::launch_start_mask(t->kp, (const uint8_t*)dev_recs, n, start_mask, t->stream));
     if ((rc = collect_marks(t, (const uint8_t*)dev_recs, n, start_mask, nullptr, t->stream))) return rc;
-    t->assembled = false;
+    t->assembled = t->loc_valid = false;
     return KH_OK;
 }
 

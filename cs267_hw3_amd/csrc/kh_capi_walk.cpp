@@ -19,7 +19,7 @@ int kh_set_starts(kh_table* t, const uint8_t* recs, uint64_t n) {
     KH_HIP(kh::launch_load_starts(t->kp, t->stage.as<uint8_t>(), n, t->starts.as<uint64_t>(),
                                   t->ctr.as<unsigned long long>(), t->stream));
     KH_SYNC(t);
-    t->assembled = false;
+    t->assembled = t->loc_valid = false;
     t->split_ok = false;  // caller's starts may share segments (e.g. two starts on one contig)
     t->starts_explicit = true;
     return KH_OK;
@@ -27,6 +27,7 @@ int kh_set_starts(kh_table* t, const uint8_t* recs, uint64_t n) {
 
 int kh_assemble_dev(kh_table* t) {
     if (!t) return fail(KH_ERR_ARG, "null table");
+    t->loc_valid = false;  // a new text: positions in the last one mean nothing
     if (int rc = set_device(t)) return rc;
     if (int rc = join_succ(t)) return rc;
     if (int rc = clean_slots(t)) return rc;

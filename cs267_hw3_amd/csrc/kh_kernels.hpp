@@ -388,6 +388,27 @@ hipError_t launch_text_keys(const KParams& p, const uint8_t* text, uint64_t len,
                             uint64_t* tile_off, uint64_t* scratch, uint8_t* keys_out, uint32_t* pos_out,
                             unsigned long long* count_out, hipStream_t s);
 
+// Position index (kh_locate.hip): loc = one uint64 per table slot, LOC_NONE = no position; every
+// write is an atomicMin, so the smallest position given for a k-mer stays.
+static constexpr uint64_t LOC_NONE = ~0ull;
+// every window of the text: loc[slot of its k-mer] = min(., pos0 + its position); absent k-mers skipped
+hipError_t launch_loc_build(const KParams& p, const uint8_t* text, uint64_t len, TableView t, uint64_t* loc,
+                            uint64_t pos0, hipStream_t s);
+// m PACKED-byte keys, each with a value: loc[slot] = min(., value); *missing (null: none, else zeroed
+// first) = keys the table does not hold
+hipError_t launch_loc_set(const KParams& p, const uint8_t* keys, uint64_t m, const uint64_t* values, TableView t,
+                          uint64_t* loc, unsigned long long* missing, hipStream_t s);
+// m keys -> pos_out[j] = loc[slot of key j], LOC_NONE when absent (pos_out 8-byte aligned)
+hipError_t launch_loc_get(const KParams& p, const uint8_t* keys, uint64_t m, TableView t, const uint64_t* loc,
+                          uint64_t* pos_out, hipStream_t s);
+// text -> pos_out (null: none) one word per position, LOC_NONE = no window / absent / no value; counts
+// (null: none, else zeroed first): {windows, located}
+hipError_t launch_loc_text(const KParams& p, const uint8_t* text, uint64_t len, TableView t, const uint64_t* loc,
+                           uint64_t* pos_out, unsigned long long* counts, hipStream_t s);
+// text positions -> line index and column over nc ascending line starts (*total: the text's bytes)
+hipError_t launch_loc_lines(const uint64_t* pos, uint64_t m, const uint64_t* off, uint64_t nc,
+                            const unsigned long long* total, uint64_t* line_out, uint64_t* col_out, hipStream_t s);
+
 }  // namespace kh
 
 // ---- partitioned (atomic-free) bulk build ------------------------------------------------------

@@ -92,6 +92,10 @@ struct kh_table {
     uint64_t last_contigs = 0;               // n_starts seen by the last assemble
     bool assembled = false;
 
+    // ---- position index (kh_capi_locate.cpp) ------------------------------------------------
+    DevBuf loc;                // one uint64 per slot, allocated by the first kh_locate_reset / _build
+    bool loc_valid = false;    // false again wherever `assembled` changes, the table is cleared or grown
+
     // ---- route / find / text scratch (sharded path) -----------------------------------------
     DevBuf route_hist, route_off, route_scratch, route_own;
     DevBuf find_own, find_ext;                // batched find: owners of routed keys / answers in key order

@@ -466,6 +466,58 @@ class GpuShard:
         check(self.L.kh_text_keys_dev(self.h, self._p(text), n, self._p(keys), self._p(pos), self._p(count)))
         return keys[:m], pos[:m], count
 
+    # position index (kh_locate.hip): positions and values are int64 tensors holding uint64 bit
+    # patterns (-1 = KH_LOC_NONE)
+    def locate_build(self):
+        """Index this shard's own contig text: position = byte offset (kh_locate_build)."""
+        check(self.L.kh_locate_build(self.h))
+
+    def locate_reset(self):
+        check(self.L.kh_locate_reset(self.h))
+
+    def locate_set(self, keys, m, values):
+        """m keys this shard owns take their int64 value unless they hold a smaller one -> int64 [1]:
+        keys the shard does not hold (kh_locate_set_dev)."""
+        missing = torch.zeros(1, dtype=torch.int64, device=self.dev)  # the call writes nothing for m = 0
+        check(self.L.kh_locate_set_dev(self.h, self._p(keys), int(m), self._p(values), self._p(missing)))
+        return missing
+
+    def locate_answer(self, keys, m):
+        """m keys -> int64 [m]: each key's value in this shard, -1 = none (kh_locate_dev)."""
+        pos = self.zeros(m, torch.int64)
+        check(self.L.kh_locate_dev(self.h, self._p(keys), int(m), self._p(pos)))
+        return pos[:int(m)]
+
+    def locate_text(self, text):
+        """Every k-mer of the text located in this shard -> (int64 [len], -1 = none; int64 [2]: windows,
+        located) (kh_locate_text_dev)."""
+        n = text.numel()
+        pos = self.zeros(n, torch.int64)
+        counts = torch.zeros(2, dtype=torch.int64, device=self.dev)  # the call writes nothing for an empty text
+        check(self.L.kh_locate_text_dev(self.h, self._p(text), n, self._p(pos), self._p(counts)))
+        return pos[:n], counts
+
+    def locate_lines(self, pos):
+        """int64 [m] positions in this shard's contig text -> (line, column) int64 [m] (kh_locate_lines_dev)."""
+        m = pos.numel()
+        line, col = self.zeros(m, torch.int64), self.zeros(m, torch.int64)
+        check(self.L.kh_locate_lines_dev(self.h, self._p(pos), m, self._p(line), self._p(col)))
+        return line[:m], col[:m]
+
+    def own_text_keys(self):
+        """text_keys of this shard's own contig text where the last walk left it in device memory
+        (kh_contigs_text_dev: one blocking read of its size)."""
+        d, b = ctypes.c_void_p(), ctypes.c_uint64(0)
+        check(self.L.kh_contigs_text_dev(self.h, ctypes.byref(d), ctypes.byref(b)))
+        n = b.value
+        kp = (self.k + 3) // 4
+        m = max(n - self.k + 1, 0)
+        keys = torch.empty((max(m, 1), kp), dtype=torch.uint8, device=self.dev)
+        pos = self.zeros(m, torch.int32)
+        count = self.zeros(1, torch.int64)
+        check(self.L.kh_text_keys_dev(self.h, d if n else None, n, self._p(keys), self._p(pos), self._p(count)))
+        return keys[:m], pos[:m], count
+
     # migrating-walker rounds (fixed-size exchange slots: no device read per round)
     MSG_WORDS = _lib.MSG_WORDS
     TEXT_REC_WORDS = _lib.TEXT_REC_WORDS
@@ -958,6 +1010,115 @@ class DistributedKmerHashMap:
             c = counts.cpu().tolist()
             return ext.cpu().numpy(), int(c[0]), int(c[1])
         return ext, counts
+
+    # ---- locate: where in which rank's contig text a k-mer sits ---------------------------------
+    LOC_RANK_SHIFT = 48  # a sharded position: rank << 48 | byte offset in that rank's contig text
+
+    def locate_build(self):
+        """Build the position index across the ranks (collective, after assemble). Each rank cuts its
+        own contig text into keys and positions, groups them by owner and sends every owner its keys
+        with rank << 48 | position as their value; the owner keeps the smallest value per k-mer, so
+        a k-mer on several lines or ranks answers the same on every run. Returns the k-mers this
+        rank received that its shard does not hold (a device int64 [1]; 0 unless the table changed
+        since the walk). A rank's contig text is cut by text_keys: under 2^32 bytes per rank. One
+        rank without a forced self-exchange: the fused build over the text."""
+        sh, P = self.shard, self.P
+        if P == 1 and not self.SELF_EXCHANGE:
+            sh.locate_build()
+            return torch.zeros(1, dtype=torch.int64, device=sh.dev)
+        kp = (sh.k + 3) // 4
+        keys, pos, count = sh.own_text_keys()
+        self.syncs += 1  # own_text_keys read the text's size
+        n = int(self._host(count)[0])
+        keys = keys[:n]
+        vals = (pos[:n].long() & 0xFFFFFFFF) | (self.comm.rank << self.LOC_RANK_SHIFT)
+        gkeys, index, counts = sh.find_route(keys, P)
+        gvals = vals[index[:n].long()]
+        send, recv, _, gmax, _ = self._exchange_counts(counts)
+        m = sum(recv)
+        rkeys = torch.empty((max(m, 1), kp), dtype=torch.uint8, device=keys.device)
+        rvals = torch.empty(max(m, 1), dtype=torch.int64, device=keys.device)
+        self._all_to_all(rkeys.view(-1)[:m * kp], gkeys.view(-1)[:n * kp], [c * kp for c in recv],
+                         [c * kp for c in send], gmax * kp)
+        self._all_to_all(rvals[:m], gvals, recv, send, gmax)
+        sh.locate_reset()
+        return sh.locate_set(rkeys, m, rvals)
+
+    def _locate_split(self, v):
+        """Values int64 [n] -> (rank, position), -1 (KH_LOC_NONE) in both where there is none."""
+        none = v == -1
+        rank = torch.where(none, v, v >> self.LOC_RANK_SHIFT)
+        pos = torch.where(none, v, v & ((1 << self.LOC_RANK_SHIFT) - 1))
+        return rank, pos
+
+    def locate(self, keys):
+        """Where each key sits (collective, after locate_build; a rank's own n may be 0): keys as for
+        find() -> (rank, position): the rank whose contig text holds the k-mer and its byte offset
+        there, KH_LOC_NONE in both when the k-mer is in no shard or on no contig. A device tensor gives
+        two int64 device tensors (-1 = KH_LOC_NONE's bit pattern), a host array two numpy uint64 arrays.
+        The route -> exchange -> answer -> return shape of find(), with 8-byte answers put back in
+        key order through the route's index."""
+        sh, P = self.shard, self.P
+        kp = (sh.k + 3) // 4
+        host = not torch.is_tensor(keys)
+        if host:
+            import numpy as np
+            keys = torch.from_numpy(np.ascontiguousarray(keys, dtype=np.uint8).reshape(-1, kp))
+            if getattr(sh, "dev", None) is not None:
+                keys = keys.to(sh.dev)
+        n = keys.numel() // kp
+        keys = keys.contiguous().view(n, kp)
+        if P == 1 and not self.SELF_EXCHANGE:
+            out = sh.locate_answer(keys, n)
+        else:
+            gkeys, index, counts = sh.find_route(keys, P)
+            send, recv, _, gmax, _ = self._exchange_counts(counts)
+            m = sum(recv)
+            rkeys = torch.empty((max(m, 1), kp), dtype=torch.uint8, device=keys.device)
+            self._all_to_all(rkeys.view(-1)[:m * kp], gkeys.view(-1)[:n * kp], [c * kp for c in recv],
+                             [c * kp for c in send], gmax * kp)
+            ans = sh.locate_answer(rkeys, m)
+            back = torch.empty(max(n, 1), dtype=torch.int64, device=keys.device)
+            self._all_to_all(back[:n], ans, send, recv, gmax)
+            out = torch.empty(n, dtype=torch.int64, device=keys.device)
+            out[index[:n].long()] = back[:n]
+        rank, pos = self._locate_split(out)
+        if host:
+            import numpy as np
+            return rank.cpu().numpy().view(np.uint64), pos.cpu().numpy().view(np.uint64)
+        return rank, pos
+
+    def locate_text(self, text):
+        """locate() for every k-mer of a text (text as for find_text) -> (rank, position), one entry
+        per byte of the text, KH_LOC_NONE in both where there is no window or the k-mer is not
+        located. Collective; a rank's own text may be empty. One rank without a forced
+        self-exchange: the fused kernel."""
+        sh, P = self.shard, self.P
+        host = not torch.is_tensor(text)
+        if host:
+            import numpy as np
+            text = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else \
+                np.ascontiguousarray(text, dtype=np.uint8).ravel()
+            text = torch.from_numpy(text.copy())
+            if getattr(sh, "dev", None) is not None:
+                text = text.to(sh.dev)
+        text = text.contiguous().view(-1)
+        n = text.numel()
+        if P == 1 and not self.SELF_EXCHANGE:
+            rank, pos = self._locate_split(sh.locate_text(text)[0])
+        else:
+            keys, tpos, count = sh.text_keys(text)
+            m = int(self._host(count)[0])
+            r, p = self.locate(keys[:m])
+            at = tpos[:m].long() & 0xFFFFFFFF
+            rank = torch.full((n,), -1, dtype=torch.int64, device=text.device)
+            pos = torch.full((n,), -1, dtype=torch.int64, device=text.device)
+            rank[at] = r
+            pos[at] = p
+        if host:
+            import numpy as np
+            return rank.cpu().numpy().view(np.uint64), pos.cpu().numpy().view(np.uint64)
+        return rank, pos
 
     def assemble(self, total_kmers):
         """Walk this rank's start k-mers (collective); returns the number of rounds. Walks that

@@ -104,6 +104,7 @@ class KmerHashTable:
         self.k = k
         self.P = packed_size(k)
         self.R = record_size(k)
+        self._device = device
         self._L = _lib.lib()
         h = ctypes.c_void_p()
         check(self._L.kh_create(ctypes.byref(h), k, int(n_kmers), float(load_factor), device))
@@ -200,6 +201,82 @@ class KmerHashTable:
         check(self._L.kh_find_text_dev(self._h, ctypes.c_void_p(text_ptr) if text_ptr else None, int(nbytes),
                                        ctypes.c_void_p(ext_ptr) if ext_ptr else None,
                                        ctypes.c_void_p(counts_ptr) if counts_ptr else None))
+
+    # -- locate: the position index (kh_locate_*) ----------------------------------------------
+    def locate_build(self):
+        """Index every k-mer of the table's own contig text (after assemble): its position is its byte
+        offset in contigs_text(), the smallest one when it stands on several lines."""
+        check(self._L.kh_locate_build(self._h))
+
+    def locate_reset(self):
+        """An empty index (every k-mer without a position), ready for locate_set_dev."""
+        check(self._L.kh_locate_reset(self._h))
+
+    def locate_drop(self):
+        """Free the index's device memory (capacity * 8 bytes)."""
+        check(self._L.kh_locate_drop(self._h))
+
+    def locate(self, keys):
+        """pkmer_t keys -> uint64 [n]: each key's position, LOC_NONE when the table does not hold it or
+        it stands on no contig."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint8)
+        n = keys.size // self.P
+        pos = np.empty(n, dtype=np.uint64)
+        check(self._L.kh_locate(self._h, _ptr(keys) if n else None, n, _ptr(pos)))
+        return pos
+
+    def locate_text(self, text):
+        """Every k-mer of a text (bytes or a numpy uint8 array) -> (pos uint64 [len], windows, located):
+        pos[i] = the position of the k-mer at bytes i .. i+k-1, LOC_NONE where there is no window, the
+        k-mer is absent or it has no position."""
+        buf = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else \
+            np.ascontiguousarray(text, dtype=np.uint8).ravel()
+        pos = np.empty(buf.size, dtype=np.uint64)
+        counts = np.zeros(2, dtype=np.uint64)
+        check(self._L.kh_locate_text(self._h, _ptr(buf) if buf.size else None, buf.size, _ptr(pos), _ptr(counts)))
+        return pos, int(counts[0]), int(counts[1])
+
+    def locate_lines(self, pos):
+        """Positions in the table's contig text (uint64) -> (line uint64 [n], col uint64 [n]) over the
+        last assemble's line starts; LOC_NONE gives LOC_NONE for both."""
+        pos = np.ascontiguousarray(pos, dtype=np.uint64).ravel()
+        n = pos.size
+        line, col = np.empty(n, dtype=np.uint64), np.empty(n, dtype=np.uint64)
+        L = self._L
+        d = ctypes.c_void_p()
+        check(L.kh_dev_malloc(ctypes.byref(d), 24 * max(n, 1), self._device))
+        try:
+            p = lambda j: ctypes.c_void_p(d.value + 8 * n * j)  # noqa: E731
+            check(L.kh_sync(self._h))
+            check(L.kh_memcpy_htod(p(0), _ptr(pos), 8 * n))
+            check(L.kh_locate_lines_dev(self._h, p(0), n, p(1), p(2)))
+            check(L.kh_sync(self._h))
+            check(L.kh_memcpy_dtoh(_ptr(line), p(1), 8 * n))
+            check(L.kh_memcpy_dtoh(_ptr(col), p(2), 8 * n))
+        finally:
+            L.kh_dev_free(d)
+        return line, col
+
+    def locate_dev(self, keys_ptr, n, pos_ptr):
+        """Asynchronous device form (kh_locate_dev): n keys at keys_ptr -> n uint64 at pos_ptr (8-byte
+        aligned). n = 0 writes nothing."""
+        check(self._L.kh_locate_dev(self._h, ctypes.c_void_p(keys_ptr) if keys_ptr else None, int(n),
+                                    ctypes.c_void_p(pos_ptr) if pos_ptr else None))
+
+    def locate_text_dev(self, text_ptr, nbytes, pos_ptr, counts_ptr):
+        """Asynchronous device form (kh_locate_text_dev): nbytes of text at text_ptr -> nbytes uint64 at
+        pos_ptr (0 / None: counts only) and 2 uint64 {windows, located} at counts_ptr (0 / None:
+        positions only), both 8-byte aligned. nbytes = 0 writes nothing."""
+        check(self._L.kh_locate_text_dev(self._h, ctypes.c_void_p(text_ptr) if text_ptr else None, int(nbytes),
+                                         ctypes.c_void_p(pos_ptr) if pos_ptr else None,
+                                         ctypes.c_void_p(counts_ptr) if counts_ptr else None))
+
+    def locate_set_dev(self, keys_ptr, n, values_ptr, missing_ptr=None):
+        """Asynchronous (kh_locate_set_dev): n keys at keys_ptr each take the uint64 at values_ptr unless
+        they hold a smaller one; missing_ptr (0 / None: not counted): 1 uint64, the keys the table lacks."""
+        check(self._L.kh_locate_set_dev(self._h, ctypes.c_void_p(keys_ptr) if keys_ptr else None, int(n),
+                                        ctypes.c_void_p(values_ptr) if values_ptr else None,
+                                        ctypes.c_void_p(missing_ptr) if missing_ptr else None))
 
     # -- assemble -------------------------------------------------------------------------
     def set_starts(self, recs):

@@ -154,6 +154,54 @@ int kh_contigs_text(kh_table* t, char* host_out, uint64_t cap);          /* D2H 
 int kh_contigs_text_dev(kh_table* t, const char** dev_text, uint64_t* bytes);
 int kh_contigs_offsets(kh_table* t, uint64_t* host_offsets, uint64_t n); /* line starts */
 
+/* ---- locate: where in the assembled contigs a k-mer sits ----------------------------------------
+ * A position index beside the table: one uint64 per slot (capacity * 8 bytes of device memory,
+ * counted by kh_device_bytes), allocated by the first kh_locate_reset / kh_locate_build and kept
+ * until kh_locate_drop / kh_destroy. KH_LOC_NONE (all ones) = no position. What later stages
+ * (seeding reads against the contigs, scaffolding, coverage per contig) would otherwise rebuild on
+ * the host from the downloaded contig text.
+ *   build   kh_locate_build: reset, then every k-mer of the table's own contig text (the bytes of
+ *           test_<rank>.dat, as kh_contigs_text_dev gives them) gets its byte offset in that text.
+ *           kh_locate_set_dev: caller-supplied uint64 values for pkmer_t keys (the sharded path
+ *           gives rank << 48 | offset). Every write is a minimum: a k-mer given several positions
+ *           (two lines of overlapping walks after kh_set_starts, a key set twice) keeps the
+ *           smallest, the same on every run.
+ *   query   by keys (kh_locate*) or for every position of a text (kh_locate_text*, windows as for
+ *           kh_find_text): the k-mer's value; KH_LOC_NONE when there is no window, the table does
+ *           not hold the k-mer, or it has no value (a k-mer on no contig). counts: 2 uint64
+ *           {windows, located}. kh_locate_lines_dev turns positions in the table's contig text
+ *           into {line index, column} over the last assemble's line starts (kh_contigs_offsets);
+ *           KH_LOC_NONE, or a position past the text, gives KH_LOC_NONE for both.
+ *   alignment   keys and text: any. Value, position, line, column and count buffers: 8 bytes,
+ *           else KH_ERR_ARG.
+ *   empty   m == 0 / len == 0: KH_OK, nothing written. len < K: every position KH_LOC_NONE,
+ *           counts {0, 0}.
+ *   null    a null table, a null required buffer, or both outputs of kh_locate_text* NULL:
+ *           KH_ERR_ARG; either single output may be NULL, as for kh_find_text*; dev_missing_out
+ *           may be NULL.
+ *   state   a staged insert left open: KH_ERR_STATE. set / locate / locate_text without a valid
+ *           index: KH_ERR_STATE. build / locate_lines without an assemble: KH_ERR_STATE.
+ *   invalidation   every insert entry point, kh_clear, a kh_reserve that grows, kh_set_starts,
+ *           the start collection of the routes and a new kh_assemble* / kh_mwalk_* walk make the
+ *           index invalid (its memory is kept); kh_locate_build after a walk that kh_assemble
+ *           redid internally indexes the final text.
+ *   None of these changes the slots, the start list, a walk, the contig text or what kh_find*
+ *   answers. All but kh_locate, kh_locate_text (synchronous, staged like kh_find) and
+ *   kh_locate_drop are asynchronous on the table's stream; kh_locate_build may first wait for the
+ *   walk, as kh_contigs_text_dev does. */
+#define KH_LOC_NONE 0xFFFFFFFFFFFFFFFFull
+int kh_locate_reset(kh_table* t);      /* allocate if needed, fill with NONE, index becomes valid */
+int kh_locate_drop(kh_table* t);       /* free the index's device memory; index invalid */
+int kh_locate_build(kh_table* t);      /* reset + positions = byte offsets into test_<rank>.dat */
+/* dev_missing_out: 1 uint64 (keys the table does not hold: skipped) or NULL */
+int kh_locate_set_dev(kh_table* t, const void* dev_keys, uint64_t m, const void* dev_values,
+                      void* dev_missing_out);
+int kh_locate_dev(kh_table* t, const void* dev_keys, uint64_t m, void* dev_pos_out);
+int kh_locate(kh_table* t, const uint8_t* host_keys, uint64_t m, uint64_t* host_pos_out);
+int kh_locate_text_dev(kh_table* t, const void* dev_text, uint64_t len, void* dev_pos_out, void* dev_counts_out);
+int kh_locate_text(kh_table* t, const char* host_text, uint64_t len, uint64_t* host_pos_out, uint64_t* counts2);
+int kh_locate_lines_dev(kh_table* t, const void* dev_pos, uint64_t m, void* dev_line_out, void* dev_col_out);
+
 /* ---- sharded multi-GPU path --------------------------------------------------------------------
  * One table per rank (GPU). The key space is split by an owner hash; the caller moves the buffers
  * between ranks (RCCL all-to-all over xGMI: include/cs267_hw3_amd/dist_hash_map.hpp, cs267_hw3_amd/dist.py). Replaces the per-owner batched
