@@ -409,6 +409,19 @@ hipError_t launch_loc_text(const KParams& p, const uint8_t* text, uint64_t len, 
 hipError_t launch_loc_lines(const uint64_t* pos, uint64_t m, const uint64_t* off, uint64_t nc,
                             const unsigned long long* total, uint64_t* line_out, uint64_t* col_out, hipStream_t s);
 
+// Seeds (kh_seed.hip). SEED_WORDS uint64 per read: {start of the longest run in the read, the value at
+// its first window, its length in windows, the read's located windows}; {NONE, NONE, 0, 0} = no seed.
+static constexpr int SEED_WORDS = 4;
+// pos: one word per text byte (len of them, not read when no read has a window); read r is bytes
+// [read_off[r], min(read_off[r + 1], len)), n_reads + 1 offsets; a window counts when it ends in its read
+hipError_t launch_seed_runs(const uint64_t* pos, uint64_t len, const uint64_t* read_off, uint64_t n_reads, int K,
+                            uint64_t* seeds, hipStream_t s);
+// seeds with a run whose value lies in the text: reads_per_line[line] += 1, bases_per_line[line] +=
+// run + K - 1 (either array may be null), lines as for launch_loc_lines
+hipError_t launch_seed_cov(const uint64_t* seeds, uint64_t n_reads, const uint64_t* off, uint64_t nc,
+                           const unsigned long long* total, int K, uint64_t* reads_per_line,
+                           uint64_t* bases_per_line, hipStream_t s);
+
 }  // namespace kh
 
 // ---- partitioned (atomic-free) bulk build ------------------------------------------------------

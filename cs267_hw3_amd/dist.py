@@ -504,6 +504,24 @@ class GpuShard:
         check(self.L.kh_locate_lines_dev(self.h, self._p(pos), m, self._p(line), self._p(col)))
         return line[:m], col[:m]
 
+    # seeds (kh_seed.hip): read offsets and seeds are int64 tensors holding uint64 bit patterns
+    def seed_runs(self, pos, read_off):
+        """int64 [len] positions (any values, -1 = none) and int64 [n + 1] read offsets -> int64 [n, 4]:
+        per read {start, value, run, located} of its longest run (kh_seed_runs_dev)."""
+        n = read_off.numel() - 1
+        seeds = torch.empty((max(n, 1), _lib.SEED_WORDS), dtype=torch.int64, device=self.dev)
+        check(self.L.kh_seed_runs_dev(self.h, self._p(pos), pos.numel(), self._p(read_off), n, self._p(seeds)))
+        return seeds[:n]
+
+    def seed_text(self, text, read_off):
+        """The text located in this shard, then seed_runs -> (seeds int64 [n, 4], positions int64 [len])
+        (kh_seed_text_dev)."""
+        n, m = read_off.numel() - 1, text.numel()
+        pos = self.zeros(m, torch.int64)
+        seeds = torch.empty((max(n, 1), _lib.SEED_WORDS), dtype=torch.int64, device=self.dev)
+        check(self.L.kh_seed_text_dev(self.h, self._p(text), m, self._p(read_off), n, self._p(pos), self._p(seeds)))
+        return seeds[:n], pos[:m]
+
     def own_text_keys(self):
         """text_keys of this shard's own contig text where the last walk left it in device memory
         (kh_contigs_text_dev: one blocking read of its size)."""
@@ -1119,6 +1137,48 @@ class DistributedKmerHashMap:
             import numpy as np
             return rank.cpu().numpy().view(np.uint64), pos.cpu().numpy().view(np.uint64)
         return rank, pos
+
+    def seed_reads(self, text, read_off=None):
+        """Where each read of a batch lies on the assembled contigs of every rank (collective, after
+        locate_build; a rank's own text may be empty): KmerHashTable.seed_reads' longest run per read,
+        over the (rank, position) values locate_text answers, so a run lies on one rank's contig text.
+        text as for find_text; read_off: n + 1 offsets into it (a host array or an int64 device
+        tensor), None = one read per line (hashmap.read_offsets, computed on the host). Returns
+        (start, rank, position, run, located), one entry per read: the run's start relative to the
+        read's first byte, the rank whose test_<rank>.dat holds it and its byte offset there (both
+        KH_LOC_NONE where the read has no seed), its length in windows, the read's located windows.
+        A device text gives int64 device tensors (-1 = KH_LOC_NONE's bit pattern), a host text numpy
+        uint64 arrays. The positions take locate_text's route; the raw rank << 48 | position words go
+        to kh_seed_runs_dev on the asking rank. One rank without a forced self-exchange:
+        kh_seed_text_dev. Coverage per contig across shards (kh_seed_coverage_dev with lines of other
+        ranks) is not built: out of scope."""
+        import numpy as np
+        from .hashmap import read_offsets
+        sh, P = self.shard, self.P
+        host = not torch.is_tensor(text)
+        if host:
+            text = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else \
+                np.ascontiguousarray(text, dtype=np.uint8).ravel()
+            text = torch.from_numpy(text.copy())
+            if getattr(sh, "dev", None) is not None:
+                text = text.to(sh.dev)
+        text = text.contiguous().view(-1)
+        if read_off is None:
+            read_off = read_offsets(self._host(text).numpy())
+        if not torch.is_tensor(read_off):
+            read_off = torch.from_numpy(np.ascontiguousarray(read_off, dtype=np.uint64).ravel().view(np.int64).copy())
+        read_off = read_off.to(text.device).contiguous().view(-1)
+        if P == 1 and not self.SELF_EXCHANGE:
+            seeds = sh.seed_text(text, read_off)[0]
+        else:
+            rank, pos = self.locate_text(text)
+            raw = torch.where(rank == -1, rank, (rank << self.LOC_RANK_SHIFT) | pos)
+            seeds = sh.seed_runs(raw, read_off)
+        rank, pos = self._locate_split(seeds[:, 1])
+        out = (seeds[:, 0], rank, pos, seeds[:, 2], seeds[:, 3])
+        if host:
+            return tuple(x.cpu().numpy().view(np.uint64) for x in out)
+        return tuple(x.contiguous() for x in out)
 
     def assemble(self, total_kmers):
         """Walk this rank's start k-mers (collective); returns the number of rounds. Walks that

@@ -91,6 +91,19 @@ def next_kmer(k, rec):
     return out
 
 
+def read_offsets(text):
+    """The reads of a text, one per line -> uint64 [n + 1] offsets (read r = bytes off[r] .. off[r+1]-1):
+    every '\\n'-terminated line is a read, its '\\n' included (a '\\r' before it too); a non-empty tail
+    without '\\n' is a last read. Empty text gives [0]."""
+    buf = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else \
+        np.ascontiguousarray(text, dtype=np.uint8).ravel()
+    ends = np.flatnonzero(buf == 10).astype(np.uint64) + np.uint64(1)
+    off = np.concatenate([np.zeros(1, np.uint64), ends])
+    if len(buf) and (not len(ends) or int(ends[-1]) != len(buf)):
+        off = np.concatenate([off, np.array([len(buf)], np.uint64)])
+    return off
+
+
 def device_count():
     n = ctypes.c_int(0)
     rc = _lib.lib().kh_device_count(ctypes.byref(n))
@@ -278,6 +291,75 @@ class KmerHashTable:
                                         ctypes.c_void_p(values_ptr) if values_ptr else None,
                                         ctypes.c_void_p(missing_ptr) if missing_ptr else None))
 
+    # -- seed: the longest exact run of each read on the contigs (kh_seed_*) ---------------------
+    def seed_reads(self, text, read_off=None):
+        """A batch of reads (text: bytes or a numpy uint8 array; read_off: uint64 [n + 1] offsets into
+        it, None = read_offsets(text), one read per line) -> uint64 [n, 4]: per read {start of its
+        longest run of windows that locate_text places one after the other, relative to the read's
+        first byte; the position of the run's first window; the run's length in windows; the read's
+        located windows}, {LOC_NONE, LOC_NONE, 0, 0} where no window is located. Matched bases =
+        run + k - 1. After locate_build."""
+        buf = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else \
+            np.ascontiguousarray(text, dtype=np.uint8).ravel()
+        off = read_offsets(buf) if read_off is None else np.ascontiguousarray(read_off, dtype=np.uint64).ravel()
+        if off.size == 0:
+            raise ValueError("read_off holds n + 1 offsets: at least one")
+        n = off.size - 1
+        seeds = np.empty((n, _lib.SEED_WORDS), dtype=np.uint64)
+        check(self._L.kh_seed_text(self._h, _ptr(buf) if buf.size else None, buf.size, _ptr(off), n,
+                                   _ptr(seeds) if n else None))
+        return seeds
+
+    def seed_text_dev(self, text_ptr, nbytes, read_off_ptr, n_reads, pos_ptr, seeds_ptr):
+        """Asynchronous device form (kh_seed_text_dev): nbytes of text at text_ptr and n_reads + 1 uint64
+        offsets at read_off_ptr -> 4 * n_reads uint64 at seeds_ptr; pos_ptr: nbytes uint64 of scratch,
+        the positions afterwards (all 8-byte aligned but the text). n_reads = 0 writes nothing."""
+        check(self._L.kh_seed_text_dev(self._h, ctypes.c_void_p(text_ptr) if text_ptr else None, int(nbytes),
+                                       ctypes.c_void_p(read_off_ptr) if read_off_ptr else None, int(n_reads),
+                                       ctypes.c_void_p(pos_ptr) if pos_ptr else None,
+                                       ctypes.c_void_p(seeds_ptr) if seeds_ptr else None))
+
+    def seed_runs_dev(self, pos_ptr, n, read_off_ptr, n_reads, seeds_ptr):
+        """Asynchronous (kh_seed_runs_dev): the run search alone over n uint64 positions at pos_ptr (any
+        values, LOC_NONE = not located; no index needed)."""
+        check(self._L.kh_seed_runs_dev(self._h, ctypes.c_void_p(pos_ptr) if pos_ptr else None, int(n),
+                                       ctypes.c_void_p(read_off_ptr) if read_off_ptr else None, int(n_reads),
+                                       ctypes.c_void_p(seeds_ptr) if seeds_ptr else None))
+
+    def seed_coverage_dev(self, seeds_ptr, n_reads, reads_ptr, bases_ptr):
+        """Asynchronous (kh_seed_coverage_dev): n_reads seeds at seeds_ptr add to the n_contigs uint64 at
+        reads_ptr (reads per contig line) and bases_ptr (their matched bases); either may be 0 / None."""
+        check(self._L.kh_seed_coverage_dev(self._h, ctypes.c_void_p(seeds_ptr) if seeds_ptr else None, int(n_reads),
+                                           ctypes.c_void_p(reads_ptr) if reads_ptr else None,
+                                           ctypes.c_void_p(bases_ptr) if bases_ptr else None))
+
+    def seed_coverage(self, seeds):
+        """Seeds uint64 [n, 4] (seed_reads) -> (reads uint64 [n_contigs], bases uint64 [n_contigs]) per
+        line of contigs_text(), counted from zero: the reads whose seed lies on the line and the bases
+        those seeds match."""
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1, _lib.SEED_WORDS)
+        n = len(seeds)
+        L = self._L
+        d = ctypes.c_void_p()
+        check(L.kh_seed_coverage_dev(self._h, None, 0, None, None))  # the state errors, whatever n is
+        nc = self.stats()["n_contigs"]
+        out = np.zeros((2, nc), dtype=np.uint64)
+        if n == 0 or nc == 0:
+            return out[0], out[1]
+        sb = 8 * _lib.SEED_WORDS * n
+        check(L.kh_dev_malloc(ctypes.byref(d), sb + 16 * nc, self._device))
+        try:
+            p = lambda o: ctypes.c_void_p(d.value + o)  # noqa: E731
+            check(L.kh_sync(self._h))
+            check(L.kh_memcpy_htod(p(0), _ptr(seeds), sb))
+            check(L.kh_memcpy_htod(p(sb), _ptr(out), 16 * nc))
+            check(L.kh_seed_coverage_dev(self._h, p(0), n, p(sb), p(sb + 8 * nc)))
+            check(L.kh_sync(self._h))
+            check(L.kh_memcpy_dtoh(_ptr(out), p(sb), 16 * nc))
+        finally:
+            L.kh_dev_free(d)
+        return out[0], out[1]
+
     # -- assemble -------------------------------------------------------------------------
     def set_starts(self, recs):
         recs, n = self._recs(recs)
@@ -374,4 +456,4 @@ class SyntheticKmers:
 
 __all__ = ["KmerHashTable", "SyntheticKmers", "KmerHashError", "pack_text", "read_kmers", "read_kmer_lines",
            "kmer_size", "pack_kmer", "unpack_kmer", "djb2", "next_kmer", "device_count",
-           "packed_size", "record_size"]
+           "packed_size", "record_size", "read_offsets"]

@@ -202,6 +202,61 @@ int kh_locate_text_dev(kh_table* t, const void* dev_text, uint64_t len, void* de
 int kh_locate_text(kh_table* t, const char* host_text, uint64_t len, uint64_t* host_pos_out, uint64_t* counts2);
 int kh_locate_lines_dev(kh_table* t, const void* dev_pos, uint64_t m, void* dev_line_out, void* dev_col_out);
 
+/* ---- seed: where a read lies on the contigs ------------------------------------------------------
+ * The consumer of the position index: for each read of a batch, the longest stretch that matches a
+ * contig exactly, found on the device from the positions kh_locate_text_dev answers, and the coverage
+ * per contig line those seeds give. Reverse complements are not looked at (the reference has none).
+ *   text    len bytes, any alignment, as for kh_locate_text*.
+ *   reads   read_off: n_reads + 1 uint64 on the device, 8-byte aligned, non-decreasing. Read r is the
+ *           bytes [read_off[r], min(read_off[r+1], len)), empty when that range is empty; bytes
+ *           outside every read are ignored. The offsets are clamped: nothing past len or past
+ *           read_off[n_reads] is read, whatever they hold.
+ *   counted window of read r: a position i with a window in the kh_find_text sense (bytes i .. i+K-1
+ *           in the text, each one of A C G T) and i + K <= the end of read r. A window that reaches
+ *           into the next read is not counted, separator byte or not.
+ *   value   v[i]: what kh_locate_text_dev answers at i; KH_LOC_NONE = not located.
+ *   continuation   i continues i-1 iff both are counted windows of the same read, both are located
+ *           and v[i] == v[i-1] + 1 in 64 bits. KH_LOC_NONE never continues and is never continued
+ *           (0xFFFFFFFFFFFFFFFE + 1 is KH_LOC_NONE).
+ *   run     a maximal chain of continuations; a single located window is a run of 1. The seed of a
+ *           read is its longest run, the one with the smallest i on a tie.
+ *   answer  KH_SEED_WORDS uint64 per read: {start of the run relative to the read's first byte, v at
+ *           the run's first window, run length in windows, located counted windows of the read}; a
+ *           read without a located window (empty, shorter than K, all absent) answers
+ *           {KH_LOC_NONE, KH_LOC_NONE, 0, 0}. Matched bases = run + K - 1. A run over positions that
+ *           kh_locate_build gave lies on one contig line: the values v+1 .. v+K after a line's last
+ *           window cover its '\n', and no k-mer holds them.
+ *   kh_seed_runs_dev   the run search alone over any position array of len uint64 (the sharded path
+ *           feeds it rank << 48 | offset values). It needs no index and reads nothing of the table:
+ *           the handle supplies K and the stream. Asynchronous.
+ *   kh_seed_text_dev   kh_locate_text_dev into dev_pos_scratch (len uint64, 8-byte aligned, the
+ *           caller's; it holds the positions afterwards), then the run search, on the table's
+ *           stream; the library allocates nothing. State rules of kh_locate_text_dev: no valid index
+ *           or a staged insert left open give KH_ERR_STATE.
+ *   kh_seed_text       the synchronous host form, staged like kh_locate_text.
+ *   kh_seed_coverage_dev   per contig line of the last assemble: every seed with run > 0 whose value
+ *           lies in the table's contig text adds 1 to reads_per_line[line] and run + K - 1 to
+ *           bases_per_line[line] (64-bit atomics; line as kh_locate_lines_dev finds it). It adds to
+ *           what the arrays hold, because reads come in batches: the caller zeroes them. Both are
+ *           n_contigs uint64; either may be NULL, not both. A value of KH_LOC_NONE or past the text
+ *           is skipped. Without an assemble, or with a staged insert open: KH_ERR_STATE.
+ *           Asynchronous.
+ *   empty   n_reads == 0: KH_OK, nothing written. len == 0 with reads: every read answers the empty
+ *           answer (text, positions and scratch may then be NULL).
+ *   errors  a null table or a null required buffer, a read-offset, position, seed or per-line buffer
+ *           that is not 8-byte aligned, n_reads >= 2^32: KH_ERR_ARG.
+ *   None of these changes the slots, the start list, a walk, the contig text, the index or what
+ *   kh_find* / kh_locate* answer. */
+#define KH_SEED_WORDS 4
+int kh_seed_runs_dev(kh_table* t, const void* dev_pos, uint64_t len, const void* dev_read_off,
+                     uint64_t n_reads, void* dev_seeds_out);
+int kh_seed_text_dev(kh_table* t, const void* dev_text, uint64_t len, const void* dev_read_off,
+                     uint64_t n_reads, void* dev_pos_scratch, void* dev_seeds_out);
+int kh_seed_text(kh_table* t, const char* host_text, uint64_t len, const uint64_t* host_read_off,
+                 uint64_t n_reads, uint64_t* host_seeds_out);
+int kh_seed_coverage_dev(kh_table* t, const void* dev_seeds, uint64_t n_reads,
+                         void* dev_reads_per_line, void* dev_bases_per_line);
+
 /* ---- sharded multi-GPU path --------------------------------------------------------------------
  * One table per rank (GPU). The key space is split by an owner hash; the caller moves the buffers
  * between ranks (RCCL all-to-all over xGMI: include/cs267_hw3_amd/dist_hash_map.hpp, cs267_hw3_amd/dist.py). Replaces the per-owner batched
