@@ -54,27 +54,13 @@ def merging_walks_text(k, L, seed, every=1):
     return "".join(f"{lines[i][0]} {lines[i][1]}{lines[i][2]}\n" for i in order).encode()
 
 
-def contigs_text(k, lens, seed, order="shuffled"):
-    """Well-formed input of independent random contigs, contig i of lens[i] k-mers (lens[i] + k - 1
-    bases): bwd 'F' on each first k-mer, fwd 'F' on each last. A contig that would repeat a k-mer
-    (its own or an earlier contig's: likely at small k) is drawn again. The lines are shuffled;
-    order="first" / "last" then puts the start record of the longest contig before / after every
-    other line. Returns (text, contigs): the fixed-width text (read_kmers.hpp:54-79 lines) and the
-    contig strings in the order of their start records, which is the expected test_0.dat."""
+def contigs_lines(k, contigs, rng, order="shuffled"):
+    """The line writer of contigs_text and chain_case: the fixed-width text (read_kmers.hpp:54-79
+    lines) of the given contig strings (no k-mer twice among them), bwd 'F' on each first k-mer, fwd
+    'F' on each last, the lines shuffled with `rng`; order="first" / "last" then puts the start
+    record of the longest contig before / after every other line. Returns (text, contigs in the order
+    of their start records, which is the expected test_0.dat)."""
     assert order in ("shuffled", "first", "last")
-    rng = np.random.default_rng(seed)
-    B = "ACGT"
-    seen = set()
-    contigs = []
-    for L in lens:
-        assert L >= 1
-        while True:
-            seq = "".join(B[x] for x in rng.integers(0, 4, L + k - 1))
-            kmers = [seq[i:i + k] for i in range(L)]
-            if len(set(kmers)) == L and seen.isdisjoint(kmers):
-                break
-        seen.update(kmers)
-        contigs.append(seq)
     lines = []  # (k-mer, bwd, fwd, contig or -1 when the line is not a start record)
     for c, seq in enumerate(contigs):
         L = len(seq) - k + 1
@@ -89,6 +75,29 @@ def contigs_text(k, lens, seed, order="shuffled"):
         perm.insert(0 if order == "first" else len(perm), at)
     text = "".join(f"{lines[i][0]} {lines[i][1]}{lines[i][2]}\n" for i in perm).encode()
     return text, [contigs[lines[i][3]] for i in perm if lines[i][3] >= 0]
+
+
+def contigs_text(k, lens, seed, order="shuffled"):
+    """Well-formed input of independent random contigs, contig i of lens[i] k-mers (lens[i] + k - 1
+    bases): bwd 'F' on each first k-mer, fwd 'F' on each last. A contig that would repeat a k-mer
+    (its own or an earlier contig's: likely at small k) is drawn again. The lines are shuffled;
+    order="first" / "last" then puts the start record of the longest contig before / after every
+    other line. Returns (text, contigs): the fixed-width text (read_kmers.hpp:54-79 lines) and the
+    contig strings in the order of their start records, which is the expected test_0.dat."""
+    rng = np.random.default_rng(seed)
+    B = "ACGT"
+    seen = set()
+    contigs = []
+    for L in lens:
+        assert L >= 1
+        while True:
+            seq = "".join(B[x] for x in rng.integers(0, 4, L + k - 1))
+            kmers = [seq[i:i + k] for i in range(L)]
+            if len(set(kmers)) == L and seen.isdisjoint(kmers):
+                break
+        seen.update(kmers)
+        contigs.append(seq)
+    return contigs_lines(k, contigs, rng, order)
 
 
 def contigs_truth(contigs):
@@ -184,6 +193,161 @@ def deferred_case(k, shape, order="shuffled"):
             return text, contigs, dict(f, seed=seed)
         tried.append(dict(f, seed=seed))
     raise AssertionError(f"no seed gives shape {shape}'s preconditions at k={k}: {tried}")
+
+
+# ---- chains of an exact number of splitter segments (k_seg_chain / k_seg_jump / k_seg_fill, and the
+# sharded k_res_pass) ------------------------------------------------------------------------------
+CHAIN_SEEDS = (0, 1, 2, 3, 4, 5, 6, 7)
+
+
+def chain_contig(k, bits, S, seed, tail, first=1, seen=()):
+    """A random contig cut so that exactly S of its k-mers at chain index >= `first` are walk
+    splitters at `bits` (every prefix of a contig is a contig, and its splitters are a prefix of the
+    list). first = 1 counts every splitter (a contig's first k-mer is a start, never a splitter):
+    the chain's splitter segments when every walker stops at every splitter; first = 2^bits counts
+    those a deferring start walker stops at (k_walk_q: steps >= split_min). tail = "on": the
+    contig's last k-mer is the S-th such splitter (a last segment of one k-mer); "after": exactly
+    two k-mers follow it, neither a splitter. No k-mer twice, none from `seen`."""
+    assert tail in ("on", "after") and S >= 1 and bits >= 1 and first >= 1
+    rng = np.random.default_rng(seed)
+    B = "ACGT"
+    L0 = (S + 4) * (2 << bits) + first + 8  # about twice the k-mers S splitters take
+    for _ in range(64):
+        seq = "".join(B[x] for x in rng.integers(0, 4, L0 + k - 1))
+        sp = [i for i in walk_splitter_indices(k, seq, bits) if i >= first]
+        if len(sp) <= S:
+            continue
+        L = sp[S - 1] + (1 if tail == "on" else 3)
+        if sp[S] < L:  # (tail "after": a further splitter among the two k-mers of the tail)
+            continue
+        kmers = [seq[i:i + k] for i in range(L)]
+        if len(set(kmers)) == L and set(seen).isdisjoint(kmers):
+            return seq[:L + k - 1]
+    raise AssertionError(f"no contig of {S} splitters at k={k}, bits={bits}, seed={seed}")
+
+
+def chain_facts(k, bits, longs, fillers):
+    """What decides the segment passes' path for the contigs `longs` plus `fillers` contigs of one
+    k-mer (no non-start k-mer: starts, no splitters), from the Python mirror alone:
+    ns, n, nsp     starts, k-mers, walk splitters at `bits`;
+    S, S_deferred  per long contig, the splitter segments of its chain when every walker stops at
+                   every splitter, and when its start walker defers (splitters at index >= 2^bits);
+    deferred       n // ns <= 2^bits: kh_assemble_dev lets the start walkers defer (split_min = 2^bits);
+    serial         the segments k_seg_chain follows itself: 128 where nsp >= 16 ns, else 32;
+    adjacent, adjacent_jumped   two splitters of one chain at neighbouring indices (a segment of one
+                   k-mer inside the chain), anywhere / from the serial-th splitter segment on (the
+                   part the jump and fill passes rank), in the mode `deferred` says;
+    max_seg        the longest segment of a chain in k-mers, in that mode."""
+    ns = len(longs) + fillers
+    n = sum(len(c) - k + 1 for c in longs) + fillers
+    sps = [walk_splitter_indices(k, c, bits) for c in longs]
+    nsp = sum(len(sp) for sp in sps)
+    deferred = n // ns <= (1 << bits)
+    serial = 128 if nsp >= 16 * ns else 32
+    S_def = [[i for i in sp if i >= (1 << bits)] for sp in sps]
+    chains = S_def if deferred else sps
+    adj = [[j for j in range(len(ch) - 1) if ch[j + 1] == ch[j] + 1] for ch in chains]
+    segs = [[b - a for a, b in zip([0] + ch, ch + [len(c) - k + 1])] for c, ch in zip(longs, chains)]
+    return {"ns": ns, "n": n, "nsp": nsp, "S": [len(sp) for sp in sps], "S_deferred": [len(sp) for sp in S_def],
+            "deferred": deferred, "serial": serial, "adjacent": any(adj),
+            "adjacent_jumped": any(j >= serial - 1 for a in adj for j in a),
+            "max_seg": max(max(s) for s in segs), "long_lens": [len(c) - k + 1 for c in longs]}
+
+
+def chain_case(k, bits, S_list, fillers, order="shuffled", tail="after", deferred=False, need=None):
+    """(text, contigs, facts): one chain_contig per entry of S_list (its count of splitter segments:
+    with `deferred` the count a deferring start walker leaves, facts["S_deferred"], else facts["S"])
+    plus `fillers` contigs of one k-mer, written by contigs_lines, at the first seed of CHAIN_SEEDS
+    whose chain_facts show those counts and satisfy need(facts); fails with the tried facts if none
+    does. The contigs do not depend on `order`."""
+    B = "ACGT"
+    tried = []
+    for s in CHAIN_SEEDS:
+        seed = 9000 + 1000 * s + 37 * k + 11 * bits + sum(S_list) + 7 * len(S_list) + fillers
+        rng = np.random.default_rng(seed)
+        seen, longs = set(), []
+        for j, S in enumerate(S_list):
+            c = chain_contig(k, bits, S, 64 * seed + j, tail, (1 << bits) if deferred else 1, seen)
+            seen.update(c[i:i + k] for i in range(len(c) - k + 1))
+            longs.append(c)
+        singles = []
+        while len(singles) < fillers:
+            x = "".join(B[b] for b in rng.integers(0, 4, k))
+            if x not in seen:
+                seen.add(x)
+                singles.append(x)
+        f = dict(chain_facts(k, bits, longs, fillers), seed=seed)
+        if f["S_deferred" if deferred else "S"] == list(S_list) and (need is None or need(f)):
+            text, contigs = contigs_lines(k, longs + singles, rng, order)
+            return text, contigs, f
+        tried.append(f)
+    raise AssertionError(f"no seed gives the chain case k={k}, bits={bits}, S={S_list}, fillers={fillers}: {tried}")
+
+
+# The single-GPU chain boundaries (test_gpu_segments.py): three regimes at KH_SPLIT_BITS=2 (one
+# splitter per 4 k-mers, forced: no filter pass).
+#   many          the long contigs alone: nsp >= 16 ns (serial 128), every walker stops at every splitter;
+#   few-eager     fillers so that nsp < 16 ns (serial 32) but n // ns > 4 (split_min 0);
+#   few-deferred  2 sum(S) fillers so that n // ns <= 4: the start walkers defer (split_min 4) and the
+#                 targets count the splitters at index >= 4.
+SEG_BITS = 2
+SEG_JUMP = 64
+SEG_REGIMES = {"many": 128, "few-eager": 32, "few-deferred": 32}  # regime -> SegBuffers::serial
+
+
+def seg_targets(serial):
+    """Splitter segments of one chain: one below / at / above the serial prefix (at: exactly one
+    pending segment, its jump pointer SEG_NONE), the prefix plus one and two full jumps of 64 links,
+    and plus three jumps and one."""
+    return [serial + d for d in (-1, 0, 1, 63, 64, 65, 127, 128, 129, 3 * SEG_JUMP + 1)]
+
+
+def seg_multi(serial):
+    """Four chains in one input: several pend entries live, anchors of different contigs interleaved."""
+    return [serial - 1, serial + 1, serial + 64, serial + 129]
+
+
+def segment_case(k, regime, S_list, tail="after", order="shuffled", bits=SEG_BITS, need=None):
+    """chain_case of a regime of SEG_REGIMES with the regime's facts demanded: serial, eager or
+    deferred, and the counts of S_list in that mode."""
+    serial = SEG_REGIMES[regime]
+    total = sum(S_list)
+    fillers = {"many": 0, "few-eager": total // 16 + 1, "few-deferred": 2 * total}[regime]
+    deferred = regime == "few-deferred"
+
+    def ok(f):
+        return f["serial"] == serial and f["deferred"] == deferred and (need is None or need(f))
+
+    return chain_case(k, bits, S_list, fillers, order, tail, deferred, ok)
+
+
+SEG_SINGLE_PARAMS = [(k, regime, S, tail) for k in (19, 51) for regime, serial in SEG_REGIMES.items()
+                     for S in seg_targets(serial) for tail in ("on", "after")]
+SEG_MULTI_PARAMS = [(k, regime, order) for k in (19, 51) for regime in SEG_REGIMES
+                    for order in ("first", "last", "shuffled")]
+# segments longer than one 256-base chunk inside a jumped chain: KH_SPLIT_BITS=6, k = 51
+SEG_CHUNK_BITS = 6
+SEG_CHUNK_PARAMS = [("few-eager", 33), ("many", 129)]
+
+
+def segment_chunk_case(regime, S):
+    return segment_case(51, regime, [S], "after", "shuffled", SEG_CHUNK_BITS, lambda f: f["max_seg"] > 256)
+
+
+# The sharded chain boundaries (test_gpu_dist.py): the sharded walker stops at every splitter (the
+# count of facts["S"]), and a pointer's span grows 8-fold per k_res_pass (RES_HOPS + 1): chains that
+# finish in passes 1, 2, 3 and 4. 2 sum(S) fillers arm the short walk (k-mers / starts <= 4, the
+# splitter spacing, kh_mwalk_short) and every long contig passes its 16-base limit (abandoned).
+RES_TARGETS = (7, 8, 9, 63, 64, 65, 511, 512, 513)
+RES_MULTI = (8, 64, 512)
+RES_PARAMS = [(51, 1), (51, 2), (51, 3), (19, 2)]  # (k, ranks)
+
+
+def sharded_chain_case(k, S_list):
+    def ok(f):
+        return f["n"] // f["ns"] <= (1 << SEG_BITS) and min(f["long_lens"]) >= 20
+
+    return chain_case(k, SEG_BITS, list(S_list), 2 * sum(S_list), "shuffled", "after", False, ok)
 
 
 # ---- walker counts around the wave (64) and the queue reservation (64 x batches) ----------------

@@ -100,6 +100,111 @@ def test_split_hash_mirror():
     assert cases.walk_splitter_indices(4, "AAAAA", 4) == [1] and cases.count_walk_splitters(4, ["AAAAA", c], 0) == 0
 
 
+# ---- chains of an exact splitter-segment count (test_gpu_segments.py, test_gpu_dist.py) ------------
+def check_chain_oracle(k, text, contigs, f):
+    """The oracle's assembly of a chain case is the builder's truth, with the facts' counts."""
+    recs = ob.parse_text(k, text)
+    assert len(recs) == f["n"] and len(contigs) == f["ns"]
+    rc, got, nc, nl, _, _ = ob.assemble(k, recs)
+    assert rc == 0 and nc == f["ns"] and nl == f["n"] - nc
+    assert got == cases.contigs_truth(contigs)
+    assert f["nsp"] == cases.count_walk_splitters(k, contigs, f["bits"])
+
+
+@pytest.mark.parametrize("tail", ["on", "after"])
+@pytest.mark.parametrize("first", [1, 4])
+@pytest.mark.parametrize("S", [1, 2, 33])
+@pytest.mark.parametrize("k", [19, 51])
+def test_chain_contig_exact(k, S, first, tail):
+    """Exactly S splitters at index >= first; tail "on": the last k-mer is the S-th, "after": two
+    k-mers follow it and neither is a splitter."""
+    c = cases.chain_contig(k, 2, S, seed=k + S + first, tail=tail, first=first)
+    L = len(c) - k + 1
+    sp = [i for i in cases.walk_splitter_indices(k, c, 2) if i >= first]
+    assert len(sp) == S and len({c[i:i + k] for i in range(L)}) == L
+    assert sp[-1] == (L - 1 if tail == "on" else L - 3)
+    assert cases.chain_contig(k, 2, S, seed=k + S + first, tail=tail, first=first) == c  # (seeded)
+
+
+def test_chain_facts_by_hand():
+    """chain_facts on splitter positions read off the mirror: counts, the deferred rule (index >=
+    2^bits), adjacency and the longest segment."""
+    k, bits = 19, 2
+    c = cases.chain_contig(k, bits, 40, seed=5, tail="after")
+    sp = cases.walk_splitter_indices(k, c, bits)
+    L = len(c) - k + 1
+    f = cases.chain_facts(k, bits, [c], 0)
+    assert (f["ns"], f["n"], f["nsp"], f["S"]) == (1, L, 40, [40]) and not f["deferred"] and f["serial"] == 128
+    assert f["S_deferred"] == [sum(i >= 4 for i in sp)]
+    assert f["adjacent"] == any(b == a + 1 for a, b in zip(sp, sp[1:])) and not f["adjacent_jumped"]
+    assert f["max_seg"] == max(b - a for a, b in zip([0] + sp, sp + [L]))
+    g = cases.chain_facts(k, bits, [c], 80)  # 80 one-k-mer contigs: deferred, few splitters per start
+    assert (g["ns"], g["n"], g["nsp"]) == (81, L + 80, 40) and g["deferred"] and g["serial"] == 32
+    ch = [i for i in sp if i >= 4]
+    assert g["adjacent_jumped"] == any(ch[j + 1] == ch[j] + 1 for j in range(31, len(ch) - 1))
+
+
+@pytest.mark.parametrize("k,regime,S,tail", cases.SEG_SINGLE_PARAMS)
+def test_segment_cases_vs_oracle(k, regime, S, tail):
+    """Every single-chain case of test_gpu_segments.py: the regime's serial prefix, eager or deferred,
+    exactly S splitter segments in that mode, the tail as asked."""
+    text, contigs, f = cases.segment_case(k, regime, [S], tail)
+    check_chain_oracle(k, text, contigs, dict(f, bits=cases.SEG_BITS))
+    serial = cases.SEG_REGIMES[regime]
+    assert f["serial"] == serial and f["deferred"] == (regime == "few-deferred")
+    assert f["S_deferred" if f["deferred"] else "S"] == [S]
+    assert (f["nsp"] >= 16 * f["ns"]) == (regime == "many")
+    assert (f["n"] // f["ns"] <= 4) == (regime == "few-deferred")
+    assert f["n"] < 3000 and max(f["long_lens"]) < 2000
+    long = max(contigs, key=len)
+    sp = [i for i in cases.walk_splitter_indices(k, long, cases.SEG_BITS) if i >= (4 if f["deferred"] else 1)]
+    assert len(sp) == S and sp[-1] == len(long) - k + 1 - (1 if tail == "on" else 3)
+
+
+@pytest.mark.parametrize("regime", list(cases.SEG_REGIMES))
+def test_segment_cases_adjacent_in_jumped_part(regime):
+    """Each regime has cases with two neighbouring splitters past the serial prefix (a one-k-mer
+    segment the jump and fill passes rank): the longest target does at both k."""
+    S = cases.seg_targets(cases.SEG_REGIMES[regime])[-1]
+    for k in (19, 51):
+        assert cases.segment_case(k, regime, [S], "after")[2]["adjacent_jumped"]
+
+
+@pytest.mark.parametrize("k,regime,order", cases.SEG_MULTI_PARAMS)
+def test_segment_multi_cases_vs_oracle(k, regime, order):
+    serial = cases.SEG_REGIMES[regime]
+    text, contigs, f = cases.segment_case(k, regime, cases.seg_multi(serial), "after", order)
+    check_chain_oracle(k, text, contigs, dict(f, bits=cases.SEG_BITS))
+    assert f["serial"] == serial and f["deferred"] == (regime == "few-deferred")
+    assert f["S_deferred" if f["deferred"] else "S"] == cases.seg_multi(serial) and f["n"] < 3000
+    long = max(contigs, key=len)
+    if order != "shuffled":
+        line = text[:k + 4] if order == "first" else text[-(k + 4):]
+        assert line == f"{long[:k]} F{long[k]}\n".encode()
+    assert cases.segment_case(k, regime, cases.seg_multi(serial))[2]["seed"] == f["seed"]  # the same contigs
+
+
+@pytest.mark.parametrize("regime,S", cases.SEG_CHUNK_PARAMS)
+def test_segment_chunk_cases_vs_oracle(regime, S):
+    """KH_SPLIT_BITS=6: a chain one segment past the serial prefix with a segment of more than 256
+    k-mers (more than one 256-base chunk)."""
+    text, contigs, f = cases.segment_chunk_case(regime, S)
+    check_chain_oracle(51, text, contigs, dict(f, bits=cases.SEG_CHUNK_BITS))
+    assert f["S"] == [S] == [cases.SEG_REGIMES[regime] + 1] and not f["deferred"]
+    assert f["serial"] == cases.SEG_REGIMES[regime] and f["max_seg"] > 256 and f["n"] < 10_000
+
+
+@pytest.mark.parametrize("S_list", [(S,) for S in cases.RES_TARGETS] + [cases.RES_MULTI])
+@pytest.mark.parametrize("k", sorted({k for k, _ in cases.RES_PARAMS}))
+def test_sharded_chain_cases_vs_oracle(k, S_list):
+    """The sharded chain cases: the eager counts, k-mers / starts <= 4 (the short walk is armed) and
+    every long contig past the short walk's 16-base limit with room to spare (it is abandoned)."""
+    text, contigs, f = cases.sharded_chain_case(k, S_list)
+    check_chain_oracle(k, text, contigs, dict(f, bits=cases.SEG_BITS))
+    assert f["S"] == list(S_list) and f["n"] // f["ns"] <= 4 and min(f["long_lens"]) >= 20
+    assert f["n"] < 10_000
+
+
 # ---- the route inputs of test_gpu_route.py --------------------------------------------------------
 @pytest.mark.parametrize("n", cases.ROUTE_SIZES)
 @pytest.mark.parametrize("k", [12, 13, 19, 22, 32, 51, 60])

@@ -9,11 +9,30 @@ import pytest
 
 import cs267_hw3_amd as kh
 import oracle_bind as ob
+from cases import RES_MULTI, RES_PARAMS, RES_TARGETS, SEG_BITS, contigs_truth, sharded_chain_case
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 MANIFEST = json.load(open(os.path.join(GOLDEN, "manifest.json")))
+
+
+@pytest.fixture
+def redo_calls(monkeypatch):
+    """Counts the calls of DistributedKmerHashMap._redo (every rank's), which still go through: the
+    unsegmented walk that a reported overlap or overflow falls back to. check_ranks sees only the
+    final text, which that second walk gets right whatever the link, pred and resolve passes did; on
+    well-formed input it must not be needed."""
+    from cs267_hw3_amd import dist
+    calls = []
+    redo = dist.DistributedKmerHashMap._redo
+
+    def counted(self, total_kmers, attempt):
+        calls.append(attempt)
+        return redo(self, total_kmers, attempt)
+
+    monkeypatch.setattr(dist.DistributedKmerHashMap, "_redo", counted)
+    return calls
 
 
 def check_ranks(g, texts, P):
@@ -143,13 +162,14 @@ def test_staged_insert_words(monkeypatch, mode, k, n, chunks):
 
 
 @pytest.mark.parametrize("P", [1, 4])
-def test_sharded_skewed_c5(P):
+def test_sharded_skewed_c5(P, redo_calls):
     """C5 skew at small scale: long chains (hundreds of migrations each) among short contigs,
     every start k-mer in the first records (rank 0 owns all walkers)."""
     from cs267_hw3_amd.dist import run_threaded
     g = kh.SyntheticKmers(51, 600_000, 2, 16, 0, seed=55, n_long=4, long_len=20_000, front_starts=True)
     info = {}
     check_ranks(g, run_threaded(51, g.records(), P, info=info), P)
+    assert not redo_calls
 
 
 def test_sharded_stats_leave_no_hip_error():
@@ -173,7 +193,7 @@ def test_sharded_stats_leave_no_hip_error():
 
 
 @pytest.mark.parametrize("P", [2, 8])
-def test_sharded_host_syncs_per_step(P):
+def test_sharded_host_syncs_per_step(P, redo_calls):
     """Device-resident rounds: fixed-size exchange slots (no host read per walk round), the
     splitter chains ranked on the device from an all-gathered predecessor table (no jump rounds),
     the walk's end checked where the last step ended. C3 shape (k=51, contigs U[8,200]) over P
@@ -185,6 +205,7 @@ def test_sharded_host_syncs_per_step(P):
     check_ranks(g, run_threaded(51, g.records(), P, info=info, steps=2), P)
     assert max(info["syncs"].values()) <= 8, info["syncs"]
     assert max(info["checks"].values()) == 1, info["checks"]
+    assert not redo_calls
 
 
 @pytest.mark.parametrize("P", [1, 3, 4])
@@ -214,7 +235,7 @@ def test_sharded_small_then_large_input(P):
 
 
 @pytest.mark.parametrize("k,L,every,P", [(19, 3000, 1, 2), (51, 1500, 3, 2), (19, 2000, 2, 3)])
-def test_sharded_overlapping_walks(k, L, every, P):
+def test_sharded_overlapping_walks(k, L, every, P, redo_calls):
     """Walks that run into each other (malformed input: a k-mer with several predecessors, every
     start walking the shared tail again, kmer_hash.cpp:41-53) make a splitter segment two walks'
     successor: the segmented walk reports the overlap with its retag count exchange and every rank
@@ -229,11 +250,12 @@ def test_sharded_overlapping_walks(k, L, every, P):
     dirty_device_memory()
     texts = run_threaded(k, recs, P)
     assert b"".join(texts) == want
+    assert len(redo_calls) >= 1  # the fallback is reachable (the other tests assert it is not taken)
 
 
 @pytest.mark.parametrize("P", [1, 3])
 @pytest.mark.parametrize("n_long", [0, 2])
-def test_sharded_short_walk_first(P, n_long):
+def test_sharded_short_walk_first(P, n_long, redo_calls):
     """Short walk first (dist.py assemble): contigs shorter than the splitter spacing walk without
     splitter segments; two long chains make every rank walk again segmented (and keep doing so for
     this input: the second step goes straight to the segmented walk). Ground truth either way."""
@@ -244,13 +266,14 @@ def test_sharded_short_walk_first(P, n_long):
     for t in texts:
         check_ranks(g, t, P)
     assert all(v == bool(n_long) for v in info["segmented"].values())
+    assert not redo_calls
 
 
 
 @pytest.mark.parametrize("P", [1, 2, 3])
 @pytest.mark.parametrize("shape", ["A", "B"])
 @pytest.mark.parametrize("k", [19, 31, 51])
-def test_sharded_tiny_deferred_shapes(k, shape, P):
+def test_sharded_tiny_deferred_shapes(k, shape, P, redo_calls):
     """The one-reservation inputs of test_gpu_small.py (30 / 90 contigs of 2-8 k-mers plus one of
     120: 262-586 k-mers in all) over P logical ranks: the short walk first, abandoned for the
     segmented walk when the long contig shows, at a few hundred walkers per rank instead of
@@ -264,3 +287,32 @@ def test_sharded_tiny_deferred_shapes(k, shape, P):
     texts = run_threaded(k, recs, P)
     assert sorted(b"".join(texts).splitlines()) == sorted(want.splitlines())
     assert sum(len(t) for t in texts) == len(want)
+    assert not redo_calls
+
+
+# ---- chains of an exact splitter-segment count over the ranks ------------------------------------------
+@pytest.mark.parametrize("S_list", [(S,) for S in RES_TARGETS] + [RES_MULTI])
+@pytest.mark.parametrize("k,P", RES_PARAMS)
+def test_sharded_chain_boundaries(monkeypatch, k, P, S_list, redo_calls):
+    """One long contig of exactly 7 / 8 / 9, 63 / 64 / 65 and 511 / 512 / 513 splitter segments at
+    KH_SPLIT_BITS=2 (the sharded walker stops at every splitter), and 8, 64 and 512 together: a
+    pointer of k_res_pass spans RES_HOPS + 1 = 8 times as many segments after each pass, so these
+    chains finish in passes 1, 2, 3 and 4 and k_res_apply reads either ping-pong buffer. Twice as
+    many one-k-mer contigs as splitters: the short walk is armed (k-mers / starts <= 4) and abandoned
+    for the segmented walk on every rank. The ranks' lines together are the oracle's, from the
+    segmented walk itself (no _redo), with no missing k-mer or cycle reported."""
+    from cs267_hw3_amd.dist import run_threaded
+    monkeypatch.setenv("KH_SPLIT_BITS", str(SEG_BITS))
+    text, contigs, f = sharded_chain_case(k, S_list)
+    assert f["S"] == list(S_list) and f["n"] // f["ns"] <= 4 and min(f["long_lens"]) >= 20 and f["n"] < 10_000
+    recs = kh.pack_text(k, text)
+    rc, want, nc, _, _, _ = ob.assemble(k, recs)
+    assert rc == 0 and nc == f["ns"] and want == contigs_truth(contigs)
+    info = {}
+    texts = run_threaded(k, recs, P, info=info)
+    assert sorted(b"".join(texts).splitlines()) == sorted(want.splitlines())
+    assert sum(len(t) for t in texts) == len(want)
+    assert not redo_calls
+    assert len(info["segmented"]) == P and all(info["segmented"].values())
+    for r in range(P):
+        assert info["stats"][r]["n_missing"] == info["stats"][r]["n_cycle"] == 0, (r, info["stats"][r])

@@ -10,6 +10,7 @@ import cs267_hw3_amd as kh
 from cs267_hw3_amd import _lib
 import oracle_bind as ob
 from cases import merging_walks_text, split_hash as _split_hash
+from walk_checks import first_attempt
 
 pytestmark = pytest.mark.gpu
 
@@ -24,10 +25,14 @@ def golden(name):
     return m["k"], recs, want
 
 
-def run(k, recs, batches=1, load=0.5, n_kmers=None):
+def run(k, recs, batches=1, load=0.5, n_kmers=None, first=None):
+    """first = (want, nc) of well-formed input: the walk alone must give them before kh_assemble
+    (whose second attempt would repair a failed segment pass) is called."""
     t = kh.KmerHashTable(k, n_kmers if n_kmers is not None else max(len(recs), 1), load)
     for part in np.array_split(recs, batches):
         t.insert_all(part)
+    if first is not None:
+        first_attempt(t, len(recs), *first)
     nc, nb = t.assemble()
     text = t.contigs_text()
     assert len(text) == nb
@@ -41,7 +46,7 @@ def test_device_present():
 @pytest.mark.parametrize("name", sorted(MANIFEST))
 def test_golden_byte_identical(name):
     k, recs, want = golden(name)
-    t, got, nc = run(k, recs)
+    t, got, nc = run(k, recs, first=(want, MANIFEST[name]["contigs"]))
     assert got == want                          # test_0.dat bytes, start-node order
     s = t.stats()
     assert nc == MANIFEST[name]["contigs"] == s["n_contigs"] == s["n_starts"]
@@ -54,14 +59,14 @@ def test_golden_byte_identical(name):
 @pytest.mark.parametrize("batches", [2, 7])
 def test_multi_batch_insert_keeps_start_order(name, batches):
     k, recs, want = golden(name)
-    _, got, _ = run(k, recs, batches=batches)
+    _, got, _ = run(k, recs, batches=batches, first=(want, MANIFEST[name]["contigs"]))
     assert got == want
 
 
 @pytest.mark.parametrize("load", [0.25, 0.7, 0.95])
 def test_load_factor_does_not_change_output(load):
     k, recs, want = golden("small51")
-    _, got, _ = run(k, recs, load=load)
+    _, got, _ = run(k, recs, load=load, first=(want, MANIFEST["small51"]["contigs"]))
     assert got == want
 
 
@@ -247,7 +252,7 @@ def test_generated_vs_oracle(k, n, lmin, lmax, single, seed):
     recs = g.records()
     rc, want, nc, nl, _, _ = ob.assemble(k, recs)
     assert rc == 0
-    _, got, gnc = run(k, recs)
+    _, got, gnc = run(k, recs, first=(want, nc))
     assert got == want and gnc == nc
 
 
@@ -263,6 +268,7 @@ def test_record_successors(k):
     assert rc == 0
     with kh.KmerHashTable(k, len(recs), device=0) as t:
         t.insert_all(recs)
+        first_attempt(t, len(recs), want, nc)
         for _ in range(2):
             got_nc, _ = t.assemble()
             assert got_nc == nc and t.contigs_text() == want
@@ -273,7 +279,7 @@ def test_c2_full_size_vs_truth():
     # which the oracle matches at every smaller size above)
     g = kh.SyntheticKmers(19, 10_000_000, 200, 1374, 0, seed=19)
     recs = g.records()
-    t, got, nc = run(19, recs)
+    t, got, nc = run(19, recs, first=(g.truth(), g.num_contigs))
     assert nc == g.num_contigs
     assert got == g.truth()
     s = t.stats()
@@ -284,7 +290,7 @@ def test_c3_shape_vs_truth_30m():
     # configs[2] shape (k=51, U[8,200]) at 30M k-mers: byte-identical to the ground truth
     g = kh.SyntheticKmers(51, 30_000_000, 8, 200, 0, seed=51)
     recs = g.records()
-    _, got, nc = run(51, recs)
+    _, got, nc = run(51, recs, first=(g.truth(), g.num_contigs))
     assert nc == g.num_contigs
     assert got == g.truth()
 
@@ -300,7 +306,7 @@ def insert_mode(request, monkeypatch):
 @pytest.mark.parametrize("batches", [1, 3])
 def test_golden_both_insert_paths(insert_mode, name, batches):
     k, recs, want = golden(name)
-    t, got, _ = run(k, recs, batches=batches)
+    t, got, _ = run(k, recs, batches=batches, first=(want, MANIFEST[name]["contigs"]))
     assert got == want
     assert t.stats()["n_dup"] == 0
 
@@ -309,7 +315,7 @@ def test_golden_both_insert_paths(insert_mode, name, batches):
                                          (31, 2_000_000, 3)])
 def test_generated_both_insert_paths(insert_mode, k, n, batches):
     g = kh.SyntheticKmers(k, n, 8, 300, 10, seed=k * 7 + batches)
-    t, got, nc = run(k, g.records(), batches=batches)
+    t, got, nc = run(k, g.records(), batches=batches, first=(g.truth(), g.num_contigs))
     assert got == g.truth() and nc == g.num_contigs
     assert t.stats()["n_dup"] == 0
 
@@ -392,6 +398,7 @@ def test_gpu_splitter_segments_vs_truth(monkeypatch, k, n, lmin, lmax, bits):
     g = kh.SyntheticKmers(k, n, lmin, lmax, 5, seed=k * 7 + lmin)
     with kh.KmerHashTable(k, n) as t:
         t.insert_all(g.records())
+        first_attempt(t, n, g.truth(), g.num_contigs)
         t.assemble()
         assert t.contigs_text() == g.truth()
 
@@ -403,6 +410,7 @@ def test_gpu_splitters_off_equals_on(monkeypatch):
         monkeypatch.setenv("KH_SPLIT_BITS", bits)
         with kh.KmerHashTable(51, 1_000_000) as t:
             t.insert_all(g.records())
+            first_attempt(t, g.n, g.truth(), g.num_contigs)
             t.assemble()
             texts.append(t.contigs_text())
     assert texts[0] == texts[1] == g.truth()
@@ -425,7 +433,7 @@ def test_gpu_line_writer_vs_oracle(monkeypatch, k, n, lmin, lmax, single, bits):
     recs = g.records()
     rc, want, nc, _, _, _ = ob.assemble(k, recs)
     assert rc == 0 and want == g.truth()
-    _, got, gnc = run(k, recs)
+    _, got, gnc = run(k, recs, first=(want, nc))
     assert gnc == nc and got == want
 
 
@@ -440,6 +448,7 @@ def test_gpu_build_kernels(monkeypatch, build, k, n, load):
     g = kh.SyntheticKmers(k, n, 8, 300, 10, seed=k + n % 97)
     with kh.KmerHashTable(k, n, load) as t:
         t.insert_all(g.records())
+        first_attempt(t, n, g.truth(), g.num_contigs)
         t.assemble()
         assert t.contigs_text() == g.truth()
         s = t.stats()
@@ -451,7 +460,7 @@ def test_gpu_build_kernels(monkeypatch, build, k, n, load):
 def test_gpu_skewed_c5(k, n, n_long, long_len):
     """C5 skew on one GPU: splitter segments walk the long chains; starts first in record order."""
     g = kh.SyntheticKmers(k, n, 2, 16, 0, seed=k + n_long, n_long=n_long, long_len=long_len, front_starts=True)
-    t, got, nc = run(k, g.records())
+    t, got, nc = run(k, g.records(), first=(g.truth(), g.num_contigs))
     assert nc == g.num_contigs and got == g.truth()
 
 
@@ -475,10 +484,10 @@ def test_deferred_splitter_segments(monkeypatch, k, long_last):
         recs = np.concatenate([recs[~is_long], recs[is_long]])
     rc, want, nc, _, _, _ = ob.assemble(k, recs)
     assert rc == 0
-    _, got, got_nc = run(k, recs)
+    _, got, got_nc = run(k, recs, first=(want, nc))
     assert got_nc == nc and got == want
     monkeypatch.setenv("KH_DEBUG", "seg_eager")
-    _, got2, _ = run(k, recs)
+    _, got2, _ = run(k, recs, first=(want, nc))
     assert got2 == want
 
 
@@ -502,7 +511,7 @@ def test_gpu_hot_minimizers_vs_oracle(monkeypatch, mode, k, n, lmax, hot, motifs
     recs = g.records()
     rc, want, nc, _, _, _ = ob.assemble(k, recs)
     assert rc == 0 and want == g.truth()
-    t, got, gnc = run(k, recs, batches=batches, load=load)
+    t, got, gnc = run(k, recs, batches=batches, load=load, first=(want, nc))
     assert gnc == nc and got == want
     s = t.stats()
     assert s["n_full"] == s["n_dup"] == s["n_missing"] == 0
@@ -527,7 +536,7 @@ def test_gpu_hot_flank_vs_oracle(monkeypatch, mode, batches):
     recs = g.records()
     rc, want, nc, _, _, _ = ob.assemble(k, recs)
     assert rc == 0 and want == g.truth()
-    t, got, gnc = run(k, recs, batches=batches)
+    t, got, gnc = run(k, recs, batches=batches, first=(want, nc))
     assert gnc == nc and got == want
     s = t.stats()
     assert s["n_full"] == s["n_dup"] == s["n_missing"] == 0
@@ -544,7 +553,7 @@ def test_gpu_hot_remap_off_is_not_needed_for_random_sets():
     """Random (non-repetitive) C3-shape input: no region is remapped; only probe runs that leave
     their slice near its end take the CAS path (a few per 10^4 keys at this table size)."""
     g = kh.SyntheticKmers(51, 4_000_000, 8, 200, 0, seed=51)
-    t, got, _ = run(51, g.records())
+    t, got, _ = run(51, g.records(), first=(g.truth(), g.num_contigs))
     assert got == g.truth()
     s = t.stats()
     assert s["n_hot_regions"] == 0 and s["n_overflow"] < len(g.records()) // 1000

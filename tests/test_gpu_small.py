@@ -12,6 +12,7 @@ import pytest
 import cs267_hw3_amd as kh
 import oracle_bind as ob
 import cases
+from walk_checks import first_attempt
 
 pytestmark = pytest.mark.gpu
 
@@ -23,7 +24,9 @@ def oracle(k, recs):
 
 
 def check_table(t, n, want, nc):
-    """One assemble of table t (n k-mers in): text, contig count and lookups are the oracle's."""
+    """One assemble of table t (n k-mers in): text, contig count and lookups are the oracle's; first
+    from the walk alone (walk_checks.first_attempt: no second attempt behind it)."""
+    first_attempt(t, n, want, nc)
     got_nc, nb = t.assemble()
     got = t.contigs_text()
     s = t.stats()

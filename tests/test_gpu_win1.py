@@ -14,6 +14,7 @@ import pytest
 import cs267_hw3_amd as kh
 import oracle_bind as ob
 import cases
+from walk_checks import first_attempt
 
 pytestmark = pytest.mark.gpu
 
@@ -50,6 +51,7 @@ def small_case(k, n):
 
 
 def check_walk(t, n, want, nc):
+    first_attempt(t, n, want, nc)  # the walk alone: kh_assemble's second attempt cannot repair it
     got_nc, nb = t.assemble()
     s = t.stats()
     assert got_nc == nc == s["n_contigs"]
