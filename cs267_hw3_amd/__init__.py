@@ -6,6 +6,6 @@ this package is its Python host mirror (ctypes).
 """
 from .hashmap import (KmerHashError, KmerHashTable, SyntheticKmers, device_count, djb2,  # noqa: F401
                       kmer_size, next_kmer, pack_kmer, pack_text, packed_size, read_kmer_lines, read_kmers,
-                      read_offsets, record_size, unpack_kmer)
+                      read_offsets, record_size, reverse_complement, unpack_kmer)
 
 __version__ = "0.1.0"

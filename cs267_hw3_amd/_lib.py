@@ -58,6 +58,7 @@ TEXT_NONE = 0xFF  # KH_TEXT_NONE: find over text, no window at the position
 TEXT_TILE = 2048  # KH_TEXT_TILE: text positions per block of the text kernels
 LOC_NONE = 0xFFFFFFFFFFFFFFFF  # KH_LOC_NONE: the position index has no position
 SEED_WORDS = 4  # KH_SEED_WORDS: uint64 per read of the seed calls
+SEED_STRAND_WORDS = 6  # KH_SEED_STRAND_WORDS: uint64 per read of the seed calls over both strands
 
 _SIGS = {
     "kh_abi_version": (ctypes.c_int, []),
@@ -113,11 +114,16 @@ _SIGS = {
     "kh_locate": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp]),
     "kh_locate_text_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_vp]),
     "kh_locate_text": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_vp]),
+    "kh_locate_text_rc_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_vp]),
+    "kh_locate_text_rc": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_vp]),
     "kh_locate_lines_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_vp]),
     "kh_seed_runs_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_u64, c_vp]),
     "kh_seed_text_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_u64, c_vp, c_vp]),
     "kh_seed_text": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_u64, c_vp]),
     "kh_seed_coverage_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_vp]),
+    "kh_seed_strand_runs_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_u64, c_vp, c_u64, c_vp]),
+    "kh_seed_strand_text_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_u64, c_vp, c_vp]),
+    "kh_seed_strand_text": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_u64, c_vp]),
     "kh_mwalk_begin": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, c_u64, c_u64, c_u64, c_u64,
                                       ctypes.POINTER(c_u64)]),
     "kh_mwalk_round_dev": (ctypes.c_int, [c_vp, c_vp, c_u64, c_vp, c_u64, c_vp]),

@@ -136,6 +136,44 @@ int kh_locate_text(kh_table* t, const char* host_text, uint64_t len, uint64_t* h
     return KH_OK;
 }
 
+// The reverse-complement forms (kernel in kh_strand.hip): kh_locate_text*'s rules, word for word.
+int kh_locate_text_rc_dev(kh_table* t, const void* dev_text, uint64_t len, void* dev_pos_out, void* dev_counts_out) {
+    if (int rc = locate_open(t, true)) return rc;
+    if (!dev_pos_out && !dev_counts_out) return fail(KH_ERR_ARG, "no output buffer");
+    if (len == 0) return KH_OK;
+    if (!dev_text) return fail(KH_ERR_ARG, "null text");
+    if (!aligned8(dev_pos_out) || !aligned8(dev_counts_out))
+        return fail(KH_ERR_ARG, "positions and counts must be 8-byte aligned");
+    if (int rc = set_device(t)) return rc;
+    if (int rc = clean_slots(t)) return rc;
+    KH_HIP(kh::launch_loc_text_rc(t->kp, (const uint8_t*)dev_text, len, view(t), loc_of(t), (uint64_t*)dev_pos_out,
+                                  (unsigned long long*)dev_counts_out, t->stream));
+    return KH_OK;
+}
+
+int kh_locate_text_rc(kh_table* t, const char* host_text, uint64_t len, uint64_t* host_pos_out, uint64_t* counts2) {
+    if (int rc = locate_open(t, true)) return rc;
+    if (!host_pos_out && !counts2) return fail(KH_ERR_ARG, "no output buffer");
+    if (len == 0) return KH_OK;
+    if (!host_text) return fail(KH_ERR_ARG, "null text");
+    if (int rc = set_device(t)) return rc;
+    int rc;
+    if ((rc = t->stage.ensure(len))) return rc;
+    if (host_pos_out && (rc = t->stage2.ensure(8 * len))) return rc;
+    if ((rc = t->stage3.ensure(16))) return rc;
+    KH_HIP(hipMemcpyAsync(t->stage.p, host_text, len, hipMemcpyHostToDevice, t->stream));
+    if ((rc = kh_locate_text_rc_dev(t, t->stage.p, len, host_pos_out ? t->stage2.p : nullptr, t->stage3.p))) return rc;
+    if (host_pos_out) KH_HIP(hipMemcpyAsync(host_pos_out, t->stage2.p, 8 * len, hipMemcpyDeviceToHost, t->stream));
+    uint64_t c[2] = {0, 0};
+    KH_HIP(hipMemcpyAsync(c, t->stage3.p, 16, hipMemcpyDeviceToHost, t->stream));
+    KH_SYNC(t);
+    if (counts2) {
+        counts2[0] = c[0];
+        counts2[1] = c[1];
+    }
+    return KH_OK;
+}
+
 int kh_locate_lines_dev(kh_table* t, const void* dev_pos, uint64_t m, void* dev_line_out, void* dev_col_out) {
     if (int rc = locate_open(t, false)) return rc;
     if (!t->assembled) return fail(KH_ERR_STATE, "no assemble since the last insert/clear");

@@ -422,6 +422,17 @@ hipError_t launch_seed_cov(const uint64_t* seeds, uint64_t n_reads, const uint64
                            const unsigned long long* total, int K, uint64_t* reads_per_line,
                            uint64_t* bases_per_line, hipStream_t s);
 
+// Both strands (kh_strand.hip). launch_loc_text with the reverse complement of every window as the
+// key: pos_out[i] = the index's value of rc(window i); same outputs, counts and alignment rules.
+hipError_t launch_loc_text_rc(const KParams& p, const uint8_t* text, uint64_t len, TableView t, const uint64_t* loc,
+                              uint64_t* pos_out, unsigned long long* counts, hipStream_t s);
+// SEED_STRAND_WORDS uint64 per read: {start, value, run, strand (0 forward, 1 reverse), located forward,
+// located reverse}. pos_f: launch_loc_text's array, pos_r: launch_loc_text_rc's; a reverse run's values
+// go down by one and its value is the one at its last window; {NONE, NONE, 0, 0, 0, 0} = no seed.
+static constexpr int SEED_STRAND_WORDS = 6;
+hipError_t launch_seed_runs_strand(const uint64_t* pos_f, const uint64_t* pos_r, uint64_t len,
+                                   const uint64_t* read_off, uint64_t n_reads, int K, uint64_t* seeds, hipStream_t s);
+
 }  // namespace kh
 
 // ---- partitioned (atomic-free) bulk build ------------------------------------------------------

@@ -1,5 +1,6 @@
 // kh_text.hpp — a tile of text in LDS, shared by the kernels that work over text (kh_text.hip: find
-// over text, key extraction; kh_locate.hip: the position index's build and query): the tile's bytes
+// over text, key extraction; kh_locate.hip: the position index's build and query; kh_strand.hip: the
+// query of every window's reverse complement): the tile's bytes
 // plus a K-1 byte halo are turned ONCE into 2-bit codes (32 bases per 64-bit word, first base in the
 // top bits: a window's V is a funnel shift of three words) and a bad-byte bitmap (one bit per byte,
 // bytes past the end of the text are bad: "window at i" = no bad bit in [i, i + K), a shift and a
@@ -65,6 +66,29 @@ __device__ __forceinline__ Key text_key(const uint64_t* cw, uint32_t i, const KP
     Key k;
     k.lo = (uint64_t)x & LO_MASK;
     k.hi = (uint64_t)(x >> 62);
+    return k;
+}
+
+// the k-mer of its reverse complement (the K bases in reverse order, each code ^ 3): the same funnel
+// shift, complemented; reversing the 2-bit groups of the 128 bits (rev2_64 of the two halves, swapped)
+// brings base 0 to bits 0-1 and base K-1 to the top of the low 2K bits, the bases after the window
+// above them. W = 1 (K <= 29): the window lies in the top word, whose reversal is the whole key.
+template <int W = 2>
+__device__ __forceinline__ Key text_key_rc(const uint64_t* cw, uint32_t i, const KParams& p) {
+    const uint32_t q = i >> 5, s = 2u * (i & 31u);
+    unsigned __int128 x = ((unsigned __int128)cw[q] << 64) | cw[q + 1];
+    if (s) x = (x << s) | (cw[q + 2] >> (64u - s));
+    x = ~x;
+    Key k;
+    if constexpr (W == 1) {
+        k.lo = rev2_64((uint64_t)(x >> 64)) & p.v_mask;
+        k.hi = 0;
+        return k;
+    }
+    unsigned __int128 r = ((unsigned __int128)rev2_64((uint64_t)x) << 64) | rev2_64((uint64_t)(x >> 64));
+    r &= ((unsigned __int128)1 << (2 * p.K)) - 1;  // K <= 60
+    k.lo = (uint64_t)r & LO_MASK;
+    k.hi = (uint64_t)(r >> 62);
     return k;
 }
 

@@ -488,13 +488,15 @@ class GpuShard:
         check(self.L.kh_locate_dev(self.h, self._p(keys), int(m), self._p(pos)))
         return pos[:int(m)]
 
-    def locate_text(self, text):
+    def locate_text(self, text, rc=False):
         """Every k-mer of the text located in this shard -> (int64 [len], -1 = none; int64 [2]: windows,
-        located) (kh_locate_text_dev)."""
+        located) (kh_locate_text_dev); rc=True: the reverse complement of every window
+        (kh_locate_text_rc_dev)."""
         n = text.numel()
         pos = self.zeros(n, torch.int64)
         counts = torch.zeros(2, dtype=torch.int64, device=self.dev)  # the call writes nothing for an empty text
-        check(self.L.kh_locate_text_dev(self.h, self._p(text), n, self._p(pos), self._p(counts)))
+        call = self.L.kh_locate_text_rc_dev if rc else self.L.kh_locate_text_dev
+        check(call(self.h, self._p(text), n, self._p(pos), self._p(counts)))
         return pos[:n], counts
 
     def locate_lines(self, pos):
@@ -521,6 +523,26 @@ class GpuShard:
         seeds = torch.empty((max(n, 1), _lib.SEED_WORDS), dtype=torch.int64, device=self.dev)
         check(self.L.kh_seed_text_dev(self.h, self._p(text), m, self._p(read_off), n, self._p(pos), self._p(seeds)))
         return seeds[:n], pos[:m]
+
+    def seed_strand_runs(self, fwd, rc, read_off):
+        """int64 [len] forward and reverse-complement positions (any values, -1 = none) and int64 [n + 1]
+        read offsets -> int64 [n, 6]: per read {start, value, run, strand, located forward, located
+        reverse} (kh_seed_strand_runs_dev)."""
+        n = read_off.numel() - 1
+        seeds = torch.empty((max(n, 1), _lib.SEED_STRAND_WORDS), dtype=torch.int64, device=self.dev)
+        check(self.L.kh_seed_strand_runs_dev(self.h, self._p(fwd), self._p(rc), fwd.numel(), self._p(read_off), n,
+                                             self._p(seeds)))
+        return seeds[:n]
+
+    def seed_strand_text(self, text, read_off):
+        """The text located in this shard on both strands, then seed_strand_runs -> (seeds int64 [n, 6],
+        positions int64 [2, len]: forward, reverse complement) (kh_seed_strand_text_dev)."""
+        n, m = read_off.numel() - 1, text.numel()
+        pos = self.zeros(2 * m, torch.int64)
+        seeds = torch.empty((max(n, 1), _lib.SEED_STRAND_WORDS), dtype=torch.int64, device=self.dev)
+        check(self.L.kh_seed_strand_text_dev(self.h, self._p(text), m, self._p(read_off), n, self._p(pos),
+                                             self._p(seeds)))
+        return seeds[:n], pos[:2 * m].view(2, m)
 
     def own_text_keys(self):
         """text_keys of this shard's own contig text where the last walk left it in device memory
@@ -1106,11 +1128,16 @@ class DistributedKmerHashMap:
             return rank.cpu().numpy().view(np.uint64), pos.cpu().numpy().view(np.uint64)
         return rank, pos
 
-    def locate_text(self, text):
+    def locate_text(self, text, rc=False):
         """locate() for every k-mer of a text (text as for find_text) -> (rank, position), one entry
         per byte of the text, KH_LOC_NONE in both where there is no window or the k-mer is not
         located. Collective; a rank's own text may be empty. One rank without a forced
-        self-exchange: the fused kernel."""
+        self-exchange: the fused kernel.
+
+        rc=True: the same for the reverse complement of every window (KmerHashTable.locate_text's rc).
+        Across ranks the text is reverse-complemented on the device (a lookup table, then a flip), takes
+        the route above unchanged, and the answer u is mirrored back: w[i] = u[len - k - i] for
+        i <= len - k, KH_LOC_NONE after that."""
         sh, P = self.shard, self.P
         host = not torch.is_tensor(text)
         if host:
@@ -1123,7 +1150,16 @@ class DistributedKmerHashMap:
         text = text.contiguous().view(-1)
         n = text.numel()
         if P == 1 and not self.SELF_EXCHANGE:
-            rank, pos = self._locate_split(sh.locate_text(text)[0])
+            rank, pos = self._locate_split(sh.locate_text(text, rc=rc)[0])
+        elif rc:
+            table = torch.arange(256, dtype=torch.uint8, device=text.device)
+            table[list(b"ACGT")] = torch.tensor(list(b"TGCA"), dtype=torch.uint8, device=text.device)
+            r, p = self.locate_text(table[text.long()].flip(0))
+            m = max(n - sh.k + 1, 0)  # positions that can hold a window
+            rank = torch.full((n,), -1, dtype=torch.int64, device=text.device)
+            pos = torch.full((n,), -1, dtype=torch.int64, device=text.device)
+            rank[:m] = r[:m].flip(0)
+            pos[:m] = p[:m].flip(0)
         else:
             keys, tpos, count = sh.text_keys(text)
             m = int(self._host(count)[0])
@@ -1138,7 +1174,7 @@ class DistributedKmerHashMap:
             return rank.cpu().numpy().view(np.uint64), pos.cpu().numpy().view(np.uint64)
         return rank, pos
 
-    def seed_reads(self, text, read_off=None):
+    def seed_reads(self, text, read_off=None, strands="+"):
         """Where each read of a batch lies on the assembled contigs of every rank (collective, after
         locate_build; a rank's own text may be empty): KmerHashTable.seed_reads' longest run per read,
         over the (rank, position) values locate_text answers, so a run lies on one rank's contig text.
@@ -1151,9 +1187,18 @@ class DistributedKmerHashMap:
         uint64 arrays. The positions take locate_text's route; the raw rank << 48 | position words go
         to kh_seed_runs_dev on the asking rank. One rank without a forced self-exchange:
         kh_seed_text_dev. Coverage per contig across shards (kh_seed_coverage_dev with lines of other
-        ranks) is not built: out of scope."""
+        ranks) is not built: out of scope.
+
+        strands="both": KmerHashTable.seed_reads' strand seed per read -> (start, rank, position, run,
+        strand, located_fwd, located_rc): from locate_text(text) and locate_text(text, rc=True) and
+        kh_seed_strand_runs_dev on the asking rank, or kh_seed_strand_text_dev on one rank. The rank
+        bits ride in the values: a reverse run's values are located words of one rank, so taking its
+        smallest never borrows from them."""
         import numpy as np
         from .hashmap import read_offsets
+        if strands not in ("+", "both"):
+            raise ValueError('strands is "+" (the contigs\' strand) or "both"')
+        both = strands == "both"
         sh, P = self.shard, self.P
         host = not torch.is_tensor(text)
         if host:
@@ -1169,13 +1214,18 @@ class DistributedKmerHashMap:
             read_off = torch.from_numpy(np.ascontiguousarray(read_off, dtype=np.uint64).ravel().view(np.int64).copy())
         read_off = read_off.to(text.device).contiguous().view(-1)
         if P == 1 and not self.SELF_EXCHANGE:
-            seeds = sh.seed_text(text, read_off)[0]
+            seeds = (sh.seed_strand_text if both else sh.seed_text)(text, read_off)[0]
         else:
             rank, pos = self.locate_text(text)
             raw = torch.where(rank == -1, rank, (rank << self.LOC_RANK_SHIFT) | pos)
-            seeds = sh.seed_runs(raw, read_off)
+            if both:
+                rank, pos = self.locate_text(text, rc=True)
+                raw_rc = torch.where(rank == -1, rank, (rank << self.LOC_RANK_SHIFT) | pos)
+                seeds = sh.seed_strand_runs(raw, raw_rc, read_off)
+            else:
+                seeds = sh.seed_runs(raw, read_off)
         rank, pos = self._locate_split(seeds[:, 1])
-        out = (seeds[:, 0], rank, pos, seeds[:, 2], seeds[:, 3])
+        out = (seeds[:, 0], rank, pos) + tuple(seeds[:, j] for j in range(2, seeds.shape[1]))
         if host:
             return tuple(x.cpu().numpy().view(np.uint64) for x in out)
         return tuple(x.contiguous() for x in out)

@@ -104,6 +104,19 @@ def read_offsets(text):
     return off
 
 
+_COMPLEMENT = np.arange(256, dtype=np.uint8)
+_COMPLEMENT[list(b"ACGT")] = list(b"TGCA")
+
+
+def reverse_complement(text):
+    """The other strand of a text (bytes or a numpy uint8 array) -> bytes: the byte order reversed and
+    A<->T, C<->G swapped; every other byte (lower case, N, '\\n', ...) is kept as it is, so lines stay
+    lines, in reverse order."""
+    buf = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else \
+        np.ascontiguousarray(text, dtype=np.uint8).ravel()
+    return _COMPLEMENT[buf[::-1]].tobytes()
+
+
 def device_count():
     n = ctypes.c_int(0)
     rc = _lib.lib().kh_device_count(ctypes.byref(n))
@@ -238,15 +251,17 @@ class KmerHashTable:
         check(self._L.kh_locate(self._h, _ptr(keys) if n else None, n, _ptr(pos)))
         return pos
 
-    def locate_text(self, text):
+    def locate_text(self, text, rc=False):
         """Every k-mer of a text (bytes or a numpy uint8 array) -> (pos uint64 [len], windows, located):
         pos[i] = the position of the k-mer at bytes i .. i+k-1, LOC_NONE where there is no window, the
-        k-mer is absent or it has no position."""
+        k-mer is absent or it has no position. rc=True: the position of the window's reverse
+        complement instead (kh_locate_text_rc): the k bases in reverse order, each complemented."""
         buf = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else \
             np.ascontiguousarray(text, dtype=np.uint8).ravel()
         pos = np.empty(buf.size, dtype=np.uint64)
         counts = np.zeros(2, dtype=np.uint64)
-        check(self._L.kh_locate_text(self._h, _ptr(buf) if buf.size else None, buf.size, _ptr(pos), _ptr(counts)))
+        call = self._L.kh_locate_text_rc if rc else self._L.kh_locate_text
+        check(call(self._h, _ptr(buf) if buf.size else None, buf.size, _ptr(pos), _ptr(counts)))
         return pos, int(counts[0]), int(counts[1])
 
     def locate_lines(self, pos):
@@ -284,6 +299,13 @@ class KmerHashTable:
                                          ctypes.c_void_p(pos_ptr) if pos_ptr else None,
                                          ctypes.c_void_p(counts_ptr) if counts_ptr else None))
 
+    def locate_text_rc_dev(self, text_ptr, nbytes, pos_ptr, counts_ptr):
+        """Asynchronous device form (kh_locate_text_rc_dev): locate_text_dev for the reverse complement
+        of every window."""
+        check(self._L.kh_locate_text_rc_dev(self._h, ctypes.c_void_p(text_ptr) if text_ptr else None, int(nbytes),
+                                            ctypes.c_void_p(pos_ptr) if pos_ptr else None,
+                                            ctypes.c_void_p(counts_ptr) if counts_ptr else None))
+
     def locate_set_dev(self, keys_ptr, n, values_ptr, missing_ptr=None):
         """Asynchronous (kh_locate_set_dev): n keys at keys_ptr each take the uint64 at values_ptr unless
         they hold a smaller one; missing_ptr (0 / None: not counted): 1 uint64, the keys the table lacks."""
@@ -292,23 +314,50 @@ class KmerHashTable:
                                         ctypes.c_void_p(missing_ptr) if missing_ptr else None))
 
     # -- seed: the longest exact run of each read on the contigs (kh_seed_*) ---------------------
-    def seed_reads(self, text, read_off=None):
+    def seed_reads(self, text, read_off=None, strands="+"):
         """A batch of reads (text: bytes or a numpy uint8 array; read_off: uint64 [n + 1] offsets into
         it, None = read_offsets(text), one read per line) -> uint64 [n, 4]: per read {start of its
         longest run of windows that locate_text places one after the other, relative to the read's
         first byte; the position of the run's first window; the run's length in windows; the read's
         located windows}, {LOC_NONE, LOC_NONE, 0, 0} where no window is located. Matched bases =
-        run + k - 1. After locate_build."""
+        run + k - 1. After locate_build.
+
+        strands="both" (kh_seed_strand_text) -> uint64 [n, 6]: {start, value, run, strand, located
+        forward, located reverse}: the longer of the read's longest forward run and its longest run as
+        a reverse complement (positions going down by one), the forward one when they are equal;
+        strand 0 = forward, 1 = reverse; value = the lowest contig position of the run on either
+        strand, so the matched contig bytes are [value, value + run + k - 1);
+        {LOC_NONE, LOC_NONE, 0, 0, 0, 0} where no window is located on either strand."""
+        if strands not in ("+", "both"):
+            raise ValueError('strands is "+" (the contigs\' strand) or "both"')
         buf = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else \
             np.ascontiguousarray(text, dtype=np.uint8).ravel()
         off = read_offsets(buf) if read_off is None else np.ascontiguousarray(read_off, dtype=np.uint64).ravel()
         if off.size == 0:
             raise ValueError("read_off holds n + 1 offsets: at least one")
         n = off.size - 1
-        seeds = np.empty((n, _lib.SEED_WORDS), dtype=np.uint64)
-        check(self._L.kh_seed_text(self._h, _ptr(buf) if buf.size else None, buf.size, _ptr(off), n,
-                                   _ptr(seeds) if n else None))
+        both = strands == "both"
+        seeds = np.empty((n, _lib.SEED_STRAND_WORDS if both else _lib.SEED_WORDS), dtype=np.uint64)
+        call = self._L.kh_seed_strand_text if both else self._L.kh_seed_text
+        check(call(self._h, _ptr(buf) if buf.size else None, buf.size, _ptr(off), n, _ptr(seeds) if n else None))
         return seeds
+
+    def seed_strand_text_dev(self, text_ptr, nbytes, read_off_ptr, n_reads, pos_ptr, seeds_ptr):
+        """Asynchronous device form (kh_seed_strand_text_dev): as seed_text_dev with 6 * n_reads uint64
+        at seeds_ptr and 2 * nbytes uint64 of scratch at pos_ptr: the forward positions, then the
+        reverse-complement ones, afterwards."""
+        check(self._L.kh_seed_strand_text_dev(self._h, ctypes.c_void_p(text_ptr) if text_ptr else None, int(nbytes),
+                                              ctypes.c_void_p(read_off_ptr) if read_off_ptr else None, int(n_reads),
+                                              ctypes.c_void_p(pos_ptr) if pos_ptr else None,
+                                              ctypes.c_void_p(seeds_ptr) if seeds_ptr else None))
+
+    def seed_strand_runs_dev(self, fwd_ptr, rc_ptr, n, read_off_ptr, n_reads, seeds_ptr):
+        """Asynchronous (kh_seed_strand_runs_dev): the run search alone over two arrays of n uint64
+        (forward positions at fwd_ptr, reverse-complement ones at rc_ptr; no index needed)."""
+        check(self._L.kh_seed_strand_runs_dev(self._h, ctypes.c_void_p(fwd_ptr) if fwd_ptr else None,
+                                              ctypes.c_void_p(rc_ptr) if rc_ptr else None, int(n),
+                                              ctypes.c_void_p(read_off_ptr) if read_off_ptr else None, int(n_reads),
+                                              ctypes.c_void_p(seeds_ptr) if seeds_ptr else None))
 
     def seed_text_dev(self, text_ptr, nbytes, read_off_ptr, n_reads, pos_ptr, seeds_ptr):
         """Asynchronous device form (kh_seed_text_dev): nbytes of text at text_ptr and n_reads + 1 uint64
@@ -336,7 +385,12 @@ class KmerHashTable:
     def seed_coverage(self, seeds):
         """Seeds uint64 [n, 4] (seed_reads) -> (reads uint64 [n_contigs], bases uint64 [n_contigs]) per
         line of contigs_text(), counted from zero: the reads whose seed lies on the line and the bases
-        those seeds match."""
+        those seeds match. Seeds uint64 [n, 6] (seed_reads(strands="both")) are repacked to {start,
+        value, run, located forward + located reverse} first: their value is the lowest position of
+        the run on either strand."""
+        seeds = np.asarray(seeds, dtype=np.uint64)
+        if seeds.ndim == 2 and seeds.shape[1] == _lib.SEED_STRAND_WORDS:
+            seeds = np.concatenate([seeds[:, :3], (seeds[:, 4] + seeds[:, 5])[:, None]], axis=1)
         seeds = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1, _lib.SEED_WORDS)
         n = len(seeds)
         L = self._L

@@ -200,12 +200,17 @@ int kh_locate_dev(kh_table* t, const void* dev_keys, uint64_t m, void* dev_pos_o
 int kh_locate(kh_table* t, const uint8_t* host_keys, uint64_t m, uint64_t* host_pos_out);
 int kh_locate_text_dev(kh_table* t, const void* dev_text, uint64_t len, void* dev_pos_out, void* dev_counts_out);
 int kh_locate_text(kh_table* t, const char* host_text, uint64_t len, uint64_t* host_pos_out, uint64_t* counts2);
+/* The same for the reverse complement of every window (see "seed, both strands" below): position i
+ * answers the value kh_locate_dev gives the key of rc(window i). Rules, counts and alignment as above. */
+int kh_locate_text_rc_dev(kh_table* t, const void* dev_text, uint64_t len, void* dev_pos_out, void* dev_counts_out);
+int kh_locate_text_rc(kh_table* t, const char* host_text, uint64_t len, uint64_t* host_pos_out, uint64_t* counts2);
 int kh_locate_lines_dev(kh_table* t, const void* dev_pos, uint64_t m, void* dev_line_out, void* dev_col_out);
 
 /* ---- seed: where a read lies on the contigs ------------------------------------------------------
  * The consumer of the position index: for each read of a batch, the longest stretch that matches a
  * contig exactly, found on the device from the positions kh_locate_text_dev answers, and the coverage
- * per contig line those seeds give. Reverse complements are not looked at (the reference has none).
+ * per contig line those seeds give. These calls look at the strand the contigs are written in; the
+ * kh_seed_strand_* calls below look at both.
  *   text    len bytes, any alignment, as for kh_locate_text*.
  *   reads   read_off: n_reads + 1 uint64 on the device, 8-byte aligned, non-decreasing. Read r is the
  *           bytes [read_off[r], min(read_off[r+1], len)), empty when that range is empty; bytes
@@ -256,6 +261,60 @@ int kh_seed_text(kh_table* t, const char* host_text, uint64_t len, const uint64_
                  uint64_t n_reads, uint64_t* host_seeds_out);
 int kh_seed_coverage_dev(kh_table* t, const void* dev_seeds, uint64_t n_reads,
                          void* dev_reads_per_line, void* dev_bases_per_line);
+
+/* ---- seed, both strands: reads from the strand the contigs were not written in ---------------------
+ * A sequencer reads either strand; the table and its contigs hold one. These calls place a read by its
+ * own bases (forward) or by their reverse complement (reverse), whichever gives the longer exact run.
+ *   rc(window)   the K bases of the window in reverse order, each complemented (A<->T, C<->G; in
+ *           2-bit codes, code ^ 3).
+ *   w[i]    KH_LOC_NONE unless position i has a window in the kh_find_text sense (K bytes inside the
+ *           text, each one of A C G T); where it has one, what the index answers for rc(window i): the
+ *           value kh_locate_dev would give that key. kh_locate_text_rc* answer w for a whole text, with
+ *           counts {windows, located}, under kh_locate_text*'s rules.
+ *   v[i]    what kh_locate_text_dev answers at i.
+ *   counted windows and reads: exactly as for kh_seed_* (i + K <= the read's end, offsets clamped).
+ *   forward continuation and run: as for kh_seed_* (v[i] == v[i-1] + 1).
+ *   reverse continuation   i continues i-1 iff both are counted windows of the same read,
+ *           w[i] != KH_LOC_NONE, w[i-1] != KH_LOC_NONE and w[i-1] == w[i] + 1 in 64 bits: if rc(window
+ *           i) stands at contig position p, rc(window i+1) stands at p - 1. A window with w == 0 is
+ *           never continued (0 - 1 is KH_LOC_NONE). A reverse run is a maximal chain of them.
+ *   strand seed of a read: the longest forward run (the first on a tie) and the longest reverse run
+ *           (the first on a tie); the longer of the two, the forward one when they are equal.
+ *   answer  KH_SEED_STRAND_WORDS uint64 per read: {start, value, run, strand, located_fwd, located_rc}.
+ *           start = the run's first window relative to the read's first byte; strand = 0 forward, 1
+ *           reverse; value = v at the run's first window (forward), w at the run's LAST window
+ *           (reverse): the smallest value of the run, w[start] - (run - 1). On either strand the
+ *           matched stretch of contig text is the bytes [value, value + run + K - 1). located_fwd /
+ *           located_rc = the read's counted windows with v / w != KH_LOC_NONE. A read with no located
+ *           window on either strand answers {KH_LOC_NONE, KH_LOC_NONE, 0, 0, 0, 0}. A reverse run over
+ *           positions that kh_locate_build gave lies on one contig line, as a forward one does: the K
+ *           values after a line's last window hold no k-mer.
+ *   kh_seed_strand_runs_dev   the run search alone over two position arrays of len uint64 each (the
+ *           sharded path feeds it rank << 48 | offset values; a run's values are located words of one
+ *           rank, so the subtraction never borrows from the rank bits). It needs no index and reads
+ *           nothing of the table. Asynchronous.
+ *   kh_seed_strand_text_dev   kh_locate_text_dev into dev_pos_scratch[0, len) and
+ *           kh_locate_text_rc_dev into dev_pos_scratch[len, 2 * len) (2 * len uint64, 8-byte aligned,
+ *           the caller's; they hold v and w afterwards), then the run search, on the table's stream;
+ *           the library allocates nothing. State rules of kh_locate_text_dev.
+ *   kh_seed_strand_text       the synchronous host form, staged like kh_seed_text (16 * len bytes of
+ *           position staging).
+ *   empty, errors, state: those of kh_seed_runs_dev, kh_seed_text_dev and kh_seed_text: n_reads == 0
+ *           writes nothing; len == 0 with reads answers the empty answer (text, positions and scratch
+ *           may then be NULL); a null table or required buffer, a misaligned buffer or n_reads >= 2^32:
+ *           KH_ERR_ARG; no valid index or a staged insert left open: KH_ERR_STATE for the calls that
+ *           read the index.
+ *   coverage   kh_seed_coverage_dev takes 4-word seeds: repack {start, value, run, located_fwd +
+ *           located_rc}; value is the lowest contig position of the run on either strand.
+ *   None of these changes the slots, the start list, a walk, the contig text, the index or what any
+ *   other call answers. */
+#define KH_SEED_STRAND_WORDS 6
+int kh_seed_strand_runs_dev(kh_table* t, const void* dev_pos_fwd, const void* dev_pos_rc, uint64_t len,
+                            const void* dev_read_off, uint64_t n_reads, void* dev_seeds_out);
+int kh_seed_strand_text_dev(kh_table* t, const void* dev_text, uint64_t len, const void* dev_read_off,
+                            uint64_t n_reads, void* dev_pos_scratch /* 2*len uint64 */, void* dev_seeds_out);
+int kh_seed_strand_text(kh_table* t, const char* host_text, uint64_t len, const uint64_t* host_read_off,
+                        uint64_t n_reads, uint64_t* host_seeds_out);
 
 /* ---- sharded multi-GPU path --------------------------------------------------------------------
  * One table per rank (GPU). The key space is split by an owner hash; the caller moves the buffers
